@@ -28,11 +28,17 @@ pair_emit_kernel).  Every step ends with the ordered (point_id, polygon_id) pair
 Also reported: the dominant kernel's achieved bandwidth against the HBM roofline --
 algorithmic bytes per launch (DESIGN.md §3: classify 18 B/point; binned join 24 B/point;
 fused join 16 B/point + 8 B/pair + 12 B/tile) over its average duration measured with HIP
-events on the launch stream -- the HBM bytes the PMC counters saw for that kernel
-(profiles/pmc_join_traffic*.json, when measured on this workload and kernel), the
-PCIe-inclusive rate (points in pinned host memory, pairs back to it; never `value`), and
-a CPU baseline: the oracle's multithreaded C restatement of the reference path on a
-bounded sample (rank 0, N=1 only).
+events on the launch stream -- and the HBM bytes the PMC counters saw for that kernel
+(profiles/pmc_join_traffic*.json, when measured on this workload and kernel).
+
+A plain run sets up, warms up, times `--steps` steps and prints the line.  `--full` adds
+what takes runs of its own (rank 0, N=1 only): the PCIe-inclusive rate (points in pinned
+host memory, pairs back to it; never `value`) and a CPU baseline, the oracle's
+multithreaded C restatement of the reference path on a bounded sample.
+
+`--dump-outputs DIR` writes what the last timed step returned -- the ordered
+(point_id, polygon_id) pairs, or a seeded sample of them -- as DIR/<name>.npy (float64);
+the inputs depend on the arguments alone, so two builds can be compared row for row.
 """
 import argparse
 import json
@@ -70,13 +76,22 @@ def parse():
                          "c4 (BNG), c5 (skewed)")
     ap.add_argument("--res", type=int, default=None, help="default: 9 (c2, c5), 10 (c3), 4 (c4)")
     ap.add_argument("--seed", type=int, default=0x20250314)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pcie", action="store_true", help="skip the PCIe-inclusive measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what takes runs of its own: the PCIe-inclusive "
+                         "rate and the CPU baseline (rank 0, --gpus 1 only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-pcie", action="store_true", help="with --full: skip the PCIe-inclusive measurement")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline sample duration")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one returned (the ordered pairs, or a "
+                         "seeded sample of them) as DIR/<name>.npy")
     ap.add_argument("--option", action="append", default=[], metavar="KEY=VALUE",
                     help="context option (mgpu_ctx_set_option, include/mosaic_gpu.h) set before the chip table "
                          "is uploaded, e.g. raster_bng=1 or pipeline=0; repeatable")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def gen_points(n, begin, seed, dev):
@@ -154,6 +169,30 @@ def pcie_inclusive(x, y, chips, res, isys, begin, cap, M, reps=3):
     return {"value": n / t, "unit": "points/s", "ms_per_step": t * 1e3,
             "bytes_over_pcie": 16 * n + 12 * m,
             "note": "points in pinned host memory, H2D copy + join + D2H copy of the pairs, median of %d" % reps}
+
+
+DUMP_MAX_PAIRS = 2_000_000  # three float64 arrays of this length: 48 MB
+
+
+def dump_outputs(path, r, seed, rank, world):
+    """What the last timed step returned, as float64 .npy files under `path` (ids below 2^53
+    are exact in float64): n_pairs, and pair_index / point_id / polygon_id -- every ordered
+    pair, or, beyond DUMP_MAX_PAIRS, the pairs at sorted positions drawn from a generator
+    seeded by the arguments alone, so two builds given the same arguments dump the same rows.
+    With N > 1 ranks each writes its own slice (<name>.rank<k>.npy)."""
+    os.makedirs(path, exist_ok=True)
+    m = len(r)
+    if m > DUMP_MAX_PAIRS:
+        idx = np.sort(np.random.default_rng([seed, rank]).integers(0, m, DUMP_MAX_PAIRS))
+    else:
+        idx = np.arange(m, dtype=np.int64)
+    sel = torch.from_numpy(idx).to(r.point_id.device)
+    arrays = {"n_pairs": np.array([m], dtype=np.float64),
+              "pair_index": idx.astype(np.float64),
+              "point_id": r.point_id.index_select(0, sel).cpu().numpy().astype(np.float64),
+              "polygon_id": r.polygon_id.index_select(0, sel).cpu().numpy().astype(np.float64)}
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + (".rank%d" % rank if world > 1 else "") + ".npy"), arr)
 
 
 def workload(a, W, M):
@@ -358,6 +397,9 @@ def main():
         off, total_pairs, _ = r.offsets
     else:
         total_pairs = pairs
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, r, a.seed, rank, world)
+        log("outputs written to %s" % a.dump_outputs)
 
     ms_step = elapsed / a.steps * 1e3
     pipeline_ms = float(np.mean(kms))
@@ -461,9 +503,10 @@ def main():
                     out["roofline"]["bound"] = "valu"
         except (ValueError, KeyError):
             pass
-    if rank == 0 and world == 1 and not a.no_pcie:
+    # (measurements that take runs of their own: only with --full)
+    if a.full and rank == 0 and world == 1 and not a.no_pcie:
         out["pcie_inclusive"] = pcie_inclusive(x, y, chips, a.res, isys, begin, cap, M)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         if table is None:
             table = M.tessellate(zones, isys, a.res, keep_core_geometries=wl.get("keep_core", True))
         log("timed; cpu baseline")

@@ -62,3 +62,41 @@ def test_traffic_key_tracks_options_table_and_source():
     assert k != B.traffic_key([], {"chips": 11890, "bytes": 60000000})
     assert B.traffic_key(["a=1", "b=2"], info) == B.traffic_key(["b=2", "a=1"], info)
     assert len(k["kernels_sha16"]) == 16
+
+
+def test_bench_plain_run_is_lean_by_default(monkeypatch):
+    """The CPU baseline and the PCIe-inclusive rate run only with --full."""
+    import bench as B
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "2"])
+    a = B.parse()
+    assert not a.full and a.dump_outputs is None and (a.steps, a.warmup) == (4, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = B.parse()
+    assert a.full and a.dump_outputs == "d"
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs: every pair of a small result; of a large one the pairs at seeded
+    positions (the same from run to run), float64, within 64 MB in all."""
+    import torch
+    import bench as B
+    from mosaic_amd.functions import JoinResult
+    r = JoinResult(torch.tensor([3, 5, 5], dtype=torch.int64), torch.tensor([7, 1, 2], dtype=torch.int32), {})
+    B.dump_outputs(str(tmp_path / "s"), r, 1, 0, 1)
+    assert np.load(tmp_path / "s" / "point_id.npy").tolist() == [3.0, 5.0, 5.0]
+    assert np.load(tmp_path / "s" / "polygon_id.npy").tolist() == [7.0, 1.0, 2.0]
+    assert np.load(tmp_path / "s" / "n_pairs.npy").tolist() == [3.0]
+    m = B.DUMP_MAX_PAIRS + 1000
+    r = JoinResult(torch.arange(m, dtype=torch.int64) * 3 + (1 << 40), (torch.arange(m) % 263).to(torch.int32), {})
+    for d in ("a", "b"):
+        B.dump_outputs(str(tmp_path / d), r, 1, 0, 1)
+    total = 0
+    for f in sorted(os.listdir(tmp_path / "a")):
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype == np.float64 and np.array_equal(x, y)
+        total += x.nbytes
+    assert total <= 64e6
+    idx = np.load(tmp_path / "a" / "pair_index.npy")
+    assert len(idx) == B.DUMP_MAX_PAIRS and (np.diff(idx) >= 0).all() and idx.max() < m
+    assert np.array_equal(np.load(tmp_path / "a" / "point_id.npy"), idx * 3 + float(1 << 40))
+    assert np.array_equal(np.load(tmp_path / "a" / "polygon_id.npy"), idx % 263)

@@ -7,7 +7,7 @@
 # Steps:
 #   tests TAG [K_EXPR]              the -m gpu suite (or the tests matching K_EXPR)
 #   smoke TAG                       __graft_entry__.smoke()
-#   bench TAG "CFGS" [ARGS]         bench.py per config (CPU baseline + PCIe line) and a
+#   bench TAG "CFGS" [ARGS]         bench.py --full per config (CPU baseline + PCIe line) and a
 #                                   rocprofv3 kernel trace of the same command (kt_TAG_<cfg>/)
 #   ktrace TAG "CFGS" [ARGS]        kernel-trace stats of bench.py only
 #   opts TAG CFG "k=v ..." ...      bench.py on CFG once per option set (two interleaved reps)
@@ -42,7 +42,7 @@ step_smoke() {
 step_bench() {
   local TAG=$1 CFGS=$2; shift 2
   for c in $CFGS; do
-    timeout -k 10 600 python3 -u bench.py --config $c "$@" > $O/final_${TAG}_$c.json 2> $O/final_${TAG}_$c.err || { echo "bench $c failed"; tail -5 $O/final_${TAG}_$c.err; return 1; }
+    timeout -k 10 600 python3 -u bench.py --full --config $c "$@" > $O/final_${TAG}_$c.json 2> $O/final_${TAG}_$c.err || { echo "bench $c failed"; tail -5 $O/final_${TAG}_$c.err; return 1; }
     timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_${TAG}_$c -o run -- python3 -u bench.py --config $c --no-cpu-baseline --no-pcie "$@" > $O/kt_${TAG}_$c.json 2> $O/kt_${TAG}_$c.err || { echo "trace $c failed"; return 1; }
     line $O/final_${TAG}_$c.json $c
   done
