@@ -117,6 +117,11 @@ int32_t mgpu_ctx_destroy(mgpu_ctx* ctx);
  *                     joins through the split pipeline with the grid entry as the code (a
  *                     cell of core chips, or an answer-grid square, answers its points; the
  *                     rest go to the mixed tiles) / through the fused pipeline
+ *   "count_lds_slots" mgpu_pip_join_count keeps per-workgroup LDS histograms for chip tables
+ *                     of at most this many polygons (default and maximum 4096: 48 KiB of
+ *                     counts and sums per workgroup, two workgroups per CU); larger tables go through a
+ *                     per-workgroup LDS hash table in front of global atomics; 0: every
+ *                     addition is a global atomic
  *   "raster", "raster_bng", "raster_sub", "raster_milli"
  *                     the chip-table builder of mgpu_chips_upload on this context
  *                     (mgpu_build_opts below)
@@ -237,6 +242,12 @@ int32_t mgpu_chips_destroy(mgpu_chips* chips);
 int32_t mgpu_chips_device_blob(const mgpu_chips* chips, void** device_ptr, int64_t* bytes);
 int32_t mgpu_chips_from_device_blob(mgpu_ctx* ctx, const void* device_ptr, int64_t bytes, mgpu_chips** out);
 int32_t mgpu_chips_info(const mgpu_chips* chips, int64_t* n_chips, int64_t* n_cells, int64_t* n_vertices);
+/* The distinct polygon ids of the table, ascending, into out_ids[cap] (host); *out_n =
+ * their number P.  These are the slots of mgpu_pip_join_count: slot k is out_ids[k].
+ * MGPU_E_CAPACITY with *out_n set if cap is short (cap 0 / out_ids NULL asks for P).  The
+ * id -> slot table is built at the first call (or the first mgpu_pip_join_count) from the
+ * table's polygon column and kept on the handle, outside the blob. */
+int32_t mgpu_chips_polygons(const mgpu_chips* chips, int32_t* out_ids, int64_t cap, int64_t* out_n);
 
 /* The chip table as one self-describing host blob (what mgpu_chips_upload uploads): a
  * JVM driver can build it once and ship the bytes to its executors, which upload them
@@ -362,6 +373,29 @@ int32_t mgpu_pip_join(mgpu_ctx* ctx, const mgpu_chips* chips, int32_t index_syst
  * MGPU_E_INVALID_ARG if no join was kept, MGPU_E_CAPACITY if capacity is still short. */
 int32_t mgpu_pip_join_fetch(mgpu_ctx* ctx, int64_t capacity, int64_t* out_n_pairs, int64_t* out_point_id,
                             int32_t* out_polygon_id, void* stream);
+
+/* The join aggregated per polygon, without the pair output: what a host does with the
+ * joined rows is most often a count (the Quickstart's joined_df.count(),
+ * docs/source/usage/quickstart.ipynb:692) or a groupBy(polygon).agg(count, sum).  For the
+ * table's distinct polygon ids ascending (mgpu_chips_polygons), count[k] = the number of
+ * pairs (point, ids[k]) mgpu_pip_join emits for the same inputs -- cell == index_id AND
+ * (is_core OR st_contains(wkb, point)), ST_Contains.scala:21-44 -- and sum[k] = the sum
+ * of weight[p] over those pairs (two's complement wrap).  A point in several overlapping
+ * polygons adds to each; polygons without points get 0.  Integer arithmetic: the results
+ * are exact and do not depend on scheduling.
+ * count / sum: device int64[n_slots]; weight: device int64[n] or NULL (then sum must be
+ * NULL, and a weight needs a sum); accumulate != 0 adds to the arrays' contents instead of
+ * overwriting them (streaming batches).  n_slots != P -> MGPU_E_INVALID_ARG.
+ * The cells are the reference's as in mgpu_pip_join (near-tie queue, host libm pass, the
+ * override rerun when a cell moves); invalid coordinates raise the same errors.  count /
+ * sum are written only after the join has settled: a failing call leaves them untouched.
+ * Synchronises `stream`; stats as mgpu_pip_join (n_pairs = the sum of the counts added;
+ * kernel_ms includes the aggregation, emit_kernel_ms is the aggregation's time).  The
+ * join's records stay in the context: mgpu_pip_join_fetch after this call writes the
+ * pairs mgpu_pip_join would have. */
+int32_t mgpu_pip_join_count(mgpu_ctx* ctx, const mgpu_chips* chips, int32_t index_system, int32_t res,
+                            const double* x, const double* y, const int64_t* weight, int64_t n, int64_t n_slots,
+                            int64_t* count, int64_t* sum, int32_t accumulate, void* stream, mgpu_stats* stats);
 
 /* Asynchronous form, in two calls.  mgpu_pip_join_async enqueues the join on `stream`
  * and returns at once: the pair count is left in device memory (*d_n_pairs, one int64)
@@ -523,6 +557,11 @@ int32_t mgpu_test_decode_point(int32_t format, const uint8_t* data, int64_t len,
  * points, candidates, ...; builds with -DMGPU_STAMPS add per-phase clock ticks of the
  * join tiles at [10..14]).  Waits for the device. */
 int32_t mgpu_test_join_counters(mgpu_ctx* ctx, uint64_t* out16);
+/* TEST ONLY: the host part of mgpu_chips_polygons (poly_slots.h) -- the distinct values
+ * of polygon_id[n] ascending into out_ids (room for n), *out_n their number, and
+ * out_slot_of_row[i] = the slot of polygon_id[i]. */
+int32_t mgpu_test_poly_slots_host(const int32_t* polygon_id, int64_t n, int32_t* out_ids, int64_t* out_n,
+                                  uint32_t* out_slot_of_row);
 
 /* TEST ONLY: the centroids of n InternalGeometryType rows (layout of
  * mgpu_internal_geometry_to_cells) on the host; status[i] 0 ok, 1 malformed, 2 unsupported,

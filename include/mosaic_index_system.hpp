@@ -15,6 +15,8 @@
 //   st_contains            ST_Contains.scala:21-44 -> MosaicGeometryJTS.contains (MosaicGeometryJTS.scala:197)
 //   pipJoin                the user-level join cell == index_id AND (is_core OR st_contains)
 //                          (notebooks/examples/python/Quickstart/QuickstartNotebook.ipynb:1835)
+//   pipJoinCount           that join aggregated per polygon (counts and integer sums), no pair
+//                          output (joined_df.count(), docs/source/usage/quickstart.ipynb:692)
 //
 // Batch methods take device pointers (HBM) and a hipStream_t (as void*); the scalar
 // forms of the reference run as a batch of one through the host-pointer entry points.
@@ -281,6 +283,15 @@ class DeviceChips {
   DeviceChips(const DeviceChips&) = delete;
   DeviceChips& operator=(const DeviceChips&) = delete;
   const mgpu_chips* get() const { return chips_; }
+  // the table's distinct polygon ids, ascending: the slots of pipJoinCount
+  std::vector<int32_t> polygons() const {
+    int64_t n = 0;
+    const int32_t st = mgpu_chips_polygons(chips_, nullptr, 0, &n);
+    if (st != MGPU_E_CAPACITY) check(st);
+    std::vector<int32_t> ids((size_t)n);
+    check(mgpu_chips_polygons(chips_, ids.data(), n, &n));
+    return ids;
+  }
 
  private:
   mgpu_chips* chips_ = nullptr;
@@ -324,6 +335,21 @@ inline JoinResult pipJoin(GpuContext& ctx, const DeviceChips& chips, const Index
     return res;
   }
   throw DeviceError("pipJoin: capacity retry failed");
+}
+
+// The join aggregated per polygon (mgpu_pip_join_count; device pointers): count_dev /
+// sum_dev hold one int64 per entry of chips.polygons(), weight_dev one int64 per point
+// (null: no sums, sum_dev null).  accumulate: add to the arrays (one call per batch of a
+// stream) instead of overwriting them.  Returns the number of pairs counted.
+inline int64_t pipJoinCount(GpuContext& ctx, const DeviceChips& chips, const IndexSystem& is, int resolution,
+                            const double* x_dev, const double* y_dev, const int64_t* weight_dev, int64_t n,
+                            int64_t n_slots, int64_t* count_dev, int64_t* sum_dev, bool accumulate = false,
+                            void* stream = nullptr) {
+  const int r = is.getResolution(resolution);
+  mgpu_stats st{};
+  check(mgpu_pip_join_count(ctx.get(), chips.get(), is.code(), r, x_dev, y_dev, weight_dev, n, n_slots, count_dev,
+                            sum_dev, accumulate ? 1 : 0, stream, &st));
+  return st.n_pairs;
 }
 
 }  // namespace mosaic

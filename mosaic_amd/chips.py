@@ -88,6 +88,28 @@ class DeviceChips:
         p, n = self.device_blob()
         return {"chips": a.value, "cells": b.value, "vertices": c.value, "bytes": n}
 
+    def polygons(self):
+        """The table's distinct polygon ids, ascending (int32 numpy array; mgpu_chips_polygons):
+        slot k of pip_join_count's arrays is polygons()[k]."""
+        if getattr(self, "_polygons", None) is not None:
+            return self._polygons
+        n = ctypes.c_int64()
+        st = N.lib().mgpu_chips_polygons(self.handle, None, 0, ctypes.byref(n))
+        if st != N.MGPU_E_CAPACITY:
+            N.check(st)
+        ids = np.zeros(n.value, np.int32)
+        N.check(N.lib().mgpu_chips_polygons(self.handle, ids.ctypes.data, n.value, ctypes.byref(n)))
+        ids.setflags(write=False)
+        self._polygons = ids
+        return ids
+
+    def polygons_device(self):
+        """polygons() as an int32 tensor on the table's device (made once)."""
+        import torch
+        if getattr(self, "_polygons_dev", None) is None:
+            self._polygons_dev = torch.from_numpy(self.polygons().copy()).to(self.ctx.device)
+        return self._polygons_dev
+
     def close(self):
         if self.handle:
             N.lib().mgpu_chips_destroy(self.handle)

@@ -21,6 +21,7 @@
 #include <limits>
 #include <string>
 #include <map>
+#include <memory>
 #include <functional>
 #include <tuple>
 #include <mutex>
@@ -36,6 +37,7 @@
 #include "kernels.h"
 #include "parallel.h"
 #include "pip_core.h"
+#include "poly_slots.h"
 #include "raster.h"
 #include "wkb.h"
 #include "capi_internal.h"
@@ -1637,10 +1639,13 @@ namespace {
 //   [tile_where u64 x T] [group_off u64 x T/32 (T)] [group_sum u32 x T/32] [dirty tiles u32 x T]
 //   [records u64 x (T * slot records + pool)]
 // counters: [0] pairs [1] route near-ties [2] invalid points [3] candidates (tile_scan_kernel)
-//           [5] pool records used [6] dirty tiles (u32) [8..] MGPU_STATS
+//           [4] kWsCountDropped (mgpu_pip_join_count's aggregation: a fused tile's records were
+//           dropped by the pool; no join kernel writes it) [5] pool records used
+//           [6] dirty tiles (u32) [7] split: extra mixed tiles (u32) [8..] MGPU_STATS
 // T = tiles of the largest point batch reserved; pool = overflow records (tiles with
 // more pairs than points), at most the output capacity.
 constexpr size_t kWsCounters = 128;  // 16 x u64
+constexpr int kWsCountDropped = 4;   // (reserved: zeroed with the counters at every join)
 
 struct WsLayout {
   size_t count, where, off, gsum, dirty, ties, recs, total;
@@ -1868,6 +1873,9 @@ int32_t mgpu_ctx_set_option(mgpu_ctx* ctx, const char* key, int64_t v) {
   } else if (k == "bng_split") {
     if (v != 0 && v != 1) return bad();
     o.bng_split = v;
+  } else if (k == "count_lds_slots") {
+    if (v < 0 || v > mgpu::kCountLdsSlotsMax) return bad();
+    o.count_lds_slots = v;
   } else if (k == "spin_us") {
     if (v < 0 || v > 10000000) return bad();
     o.spin_us = v;
@@ -1893,7 +1901,7 @@ int32_t mgpu_ctx_get_option(const mgpu_ctx* ctx, const char* key, int64_t* v) {
       {"h3_libm", o.h3_libm},       {"pipeline", o.pipeline}, {"bin_count", o.bin_count},
       {"bin_min_mb", o.bin_min_mb}, {"bin_min_points", o.bin_min_points}, {"bin_xcd", o.bin_xcd},
       {"bin_keys", o.bin_keys},     {"spin_us", o.spin_us},   {"ring_batch", o.ring_batch},       {"raster", o.raster},     {"raster_bng", o.raster_bng},
-      {"bng_split", o.bng_split},
+      {"bng_split", o.bng_split},   {"count_lds_slots", o.count_lds_slots},
       {"raster_sub", o.raster_sub}, {"raster_milli", o.raster_milli}};
   for (const auto& kv : all)
     if (strcmp(kv.first, key) == 0) {
@@ -2888,6 +2896,64 @@ int32_t mgpu_host_blob_info(const void* host_blob, int64_t bytes, int32_t* index
 
 }  // extern "C"
 
+// mgpu_pip_join_count's polygon slots of a chip table (poly_slots.h), on the device: built
+// at the first use from the table's chip_poly -- read back from the blob, so handles made
+// from a device blob or a broadcast have them too -- and kept on the handle, outside the
+// blob (mgpu_chips.slots).
+struct PolySlotsDev {
+  std::vector<int32_t> ids;        // host copy (mgpu_chips_polygons)
+  int32_t* d_ids = nullptr;        // [P]
+  uint32_t* d_chip_slot = nullptr; // [n_chips]
+  uint32_t* d_dense = nullptr;     // [max id - min id + 1] or null (poly_slots_dense)
+};
+
+static std::mutex g_slots_mu;
+
+static void free_poly_slots(mgpu_chips* chips) {
+  auto* ps = (PolySlotsDev*)chips->slots;
+  if (!ps) return;
+  if (ps->d_ids) hipFree(ps->d_ids);
+  if (ps->d_chip_slot) hipFree(ps->d_chip_slot);
+  if (ps->d_dense) hipFree(ps->d_dense);
+  delete ps;
+  chips->slots = nullptr;
+}
+
+static int32_t ensure_poly_slots(const mgpu_chips* chips, const PolySlotsDev** out) {
+  std::lock_guard<std::mutex> lock(g_slots_mu);
+  if (chips->slots) {
+    *out = (const PolySlotsDev*)chips->slots;
+    return MGPU_OK;
+  }
+  if (int32_t st = set_device(chips->device)) return st;
+  const int64_t nch = chips->view.n_chips;
+  std::vector<int32_t> poly((size_t)nch);
+  if (nch) HIP_TRY(hipMemcpy(poly.data(), chips->view.chip_poly, (size_t)nch * 4, hipMemcpyDeviceToHost));
+  mgpu::PolySlots hs = mgpu::poly_slots(poly.data(), nch);
+  auto ps = std::make_unique<PolySlotsDev>();
+  auto upload = [&](auto** d, const void* src, size_t bytes) -> hipError_t {
+    if (hipError_t e = hipMalloc((void**)d, std::max<size_t>(bytes, 4))) return e;
+    return bytes ? hipMemcpy(*d, src, bytes, hipMemcpyHostToDevice) : hipSuccess;
+  };
+  hipError_t e = upload(&ps->d_ids, hs.ids.data(), hs.ids.size() * 4);
+  if (e == hipSuccess) e = upload(&ps->d_chip_slot, hs.slot_of_row.data(), hs.slot_of_row.size() * 4);
+  if (e == hipSuccess && mgpu::poly_slots_dense(hs.ids)) {
+    std::vector<uint32_t> dense((size_t)((int64_t)hs.ids.back() - hs.ids.front() + 1), 0u);
+    for (size_t k = 0; k < hs.ids.size(); k++) dense[(size_t)((int64_t)hs.ids[k] - hs.ids.front())] = (uint32_t)k;
+    e = upload(&ps->d_dense, dense.data(), dense.size() * 4);
+  }
+  if (e != hipSuccess) {
+    if (ps->d_ids) hipFree(ps->d_ids);
+    if (ps->d_chip_slot) hipFree(ps->d_chip_slot);
+    if (ps->d_dense) hipFree(ps->d_dense);
+    return fail(MGPU_E_DEVICE, "polygon slots: %s", hipGetErrorString(e));
+  }
+  ps->ids = std::move(hs.ids);
+  chips->slots = ps.release();
+  *out = (const PolySlotsDev*)chips->slots;
+  return MGPU_OK;
+}
+
 // Host -> device copy of `bytes` bytes that fill(dst, off, n) produces, through two pinned
 // 64 MiB staging buffers: the host threads fill one piece while the DMA engine moves the
 // other (a pageable hipMemcpy of C3's 5.3 GB blob ran at ~4.6 GB/s on the box).
@@ -2988,6 +3054,7 @@ int32_t mgpu_chips_destroy(mgpu_chips* chips) {
   if (!chips) return MGPU_OK;
   hipSetDevice(chips->device);
   if (chips->blob) hipFree(chips->blob);
+  free_poly_slots(chips);
   delete chips;
   return MGPU_OK;
 }
@@ -3093,7 +3160,7 @@ static int32_t join_impl(mgpu_ctx* ctx, const mgpu_chips* chips, int32_t is, int
                          const double* y, const int64_t* point_id, int64_t id_base, int64_t n, int64_t capacity,
                          int64_t* out_point, int32_t* out_poly, hipStream_t s, bool timed,
                          const uint8_t* valid = nullptr, int64_t valid_off = 0, int64_t n_ovr = 0,
-                         int tie_host = 0) {
+                         int tie_host = 0, int64_t count_pool = -1) {
   if (!ctx || !chips) return fail(MGPU_E_INVALID_ARG, "ctx/chips is NULL");
   if (int32_t r = check_res(is, res)) return r;
   if (chips->index_system != is)
@@ -3105,8 +3172,11 @@ static int32_t join_impl(mgpu_ctx* ctx, const mgpu_chips* chips, int32_t is, int
   if (int32_t st = set_device(ctx->device)) return st;
   int64_t tiles = mgpu::join_tiles(n);
   // pool: the records of tiles with more pairs than points (bounded by the capacity; a
-  // total beyond it is reported as MGPU_E_CAPACITY either way)
-  const int64_t pool = capacity;
+  // total beyond it is reported as MGPU_E_CAPACITY either way).  Count mode
+  // (mgpu_pip_join_count, count_pool >= 0) has no capacity: its pool is count_pool, and
+  // nothing that writes pairs is launched.
+  const bool emit = count_pool < 0;
+  const int64_t pool = emit ? capacity : count_pool;
   if (int32_t st = ensure_ws(ctx, tiles, pool)) return st;
   auto* base = (uint8_t*)ctx->ws;
   const WsLayout L = ws_layout(tiles, pool);
@@ -3269,11 +3339,11 @@ static int32_t join_impl(mgpu_ctx* ctx, const mgpu_chips* chips, int32_t is, int
   }
   if (timed) HIP_TRY(hipEventRecord(ctx->ev0, s));
   if (split)
-    HIP_TRY(mgpu::launch_split(is, sa, s, timed ? ctx->ev2 : nullptr, timed ? ctx->ev3 : nullptr));
+    HIP_TRY(mgpu::launch_split(is, sa, s, timed ? ctx->ev2 : nullptr, timed ? ctx->ev3 : nullptr, emit));
   else if (binned)
-    HIP_TRY(mgpu::launch_binned(is, ba, s, timed ? ctx->ev3 : nullptr, timed ? ctx->ev2 : nullptr));
+    HIP_TRY(mgpu::launch_binned(is, ba, s, timed ? ctx->ev3 : nullptr, timed ? ctx->ev2 : nullptr, emit));
   else
-    HIP_TRY(mgpu::launch_join(is, a, e, s, timed ? ctx->ev2 : nullptr));
+    HIP_TRY(mgpu::launch_join(is, a, e, s, timed ? ctx->ev2 : nullptr, emit));
   if (timed) HIP_TRY(hipEventRecord(ctx->ev1, s));
   auto& L2 = ctx->last;
   L2.split = split;
@@ -3296,6 +3366,8 @@ static int32_t join_impl(mgpu_ctx* ctx, const mgpu_chips* chips, int32_t is, int
   L2.n_ovr = n_ovr;
   L2.tie_host = a.tie_host;
   L2.pool_ok = false;
+  L2.pool = pool;
+  L2.pool_used = 0;
   L2.total = -1;
   L2.valid = true;
   L2.stream = (void*)s;
@@ -3364,11 +3436,12 @@ struct JoinCall {
   const uint8_t* valid;
   int64_t valid_off;
   int64_t* d_n_pairs;  // the asynchronous form's device count (or null)
+  int64_t count_pool = -1;  // >= 0: mgpu_pip_join_count's join (join_impl's count mode) with this overflow pool
 };
 
 static int32_t launch_call(mgpu_ctx* ctx, const JoinCall& c, bool timed, int64_t n_ovr, int tie_host) {
   int32_t st = join_impl(ctx, c.chips, c.is, c.res, c.x, c.y, c.point_id, c.id_base, c.n, c.capacity, c.out_point,
-                         c.out_poly, c.s, timed, c.valid, c.valid_off, n_ovr, tie_host);
+                         c.out_poly, c.s, timed, c.valid, c.valid_off, n_ovr, tie_host, c.count_pool);
   if (st) return st;
   if (c.d_n_pairs) HIP_TRY(hipMemcpyAsync(c.d_n_pairs, ctx->ws, 8, hipMemcpyDeviceToDevice, c.s));
   return MGPU_OK;
@@ -3419,10 +3492,10 @@ static int32_t launch_override_pass(mgpu_ctx* ctx, const JoinCall& c, bool timed
   if (L.split) {
     mgpu::SplitArgs sa = L.sargs;
     sa.j = a;
-    HIP_TRY(mgpu::launch_split_redo(c.is, sa, R, (int64_t)list.size(), c.s));
+    HIP_TRY(mgpu::launch_split_redo(c.is, sa, R, (int64_t)list.size(), c.s, c.count_pool < 0));
     L.sargs = sa;
   } else {
-    HIP_TRY(mgpu::launch_join_redo(c.is, a, L.emit, R, (int64_t)list.size(), c.s));
+    HIP_TRY(mgpu::launch_join_redo(c.is, a, L.emit, R, (int64_t)list.size(), c.s, c.count_pool < 0));
     L.jargs = a;
   }
   if (timed) HIP_TRY(hipEventRecord(ctx->ev1, c.s));
@@ -3516,13 +3589,14 @@ static int32_t settle_join(mgpu_ctx* ctx, const JoinCall& c, bool timed, bool re
   // workspace, so a larger output can be written by mgpu_pip_join_fetch alone (the split
   // and binned pipelines keep their answers: always)
   ctx->last.total = (int64_t)h[0];
-  ctx->last.pool_ok = ctx->last.split || ctx->last.binned || (int64_t)h[5] <= capacity;
+  ctx->last.pool_used = (int64_t)h[5];
+  ctx->last.pool_ok = ctx->last.split || ctx->last.binned || (int64_t)h[5] <= ctx->last.pool;
   if (h[2]) {
     ctx->last.valid = false;
     if (is == MGPU_BNG) return fail(MGPU_E_NAN, "NaN coordinates are not supported. (%llu points)", (unsigned long long)h[2]);
     return fail(MGPU_E_INVALID_ARG, "Latitude or longitude were invalid. (%llu points)", (unsigned long long)h[2]);
   }
-  if ((int64_t)h[0] > capacity)
+  if (c.count_pool < 0 && (int64_t)h[0] > capacity)
     return fail(MGPU_E_CAPACITY, "%lld pairs do not fit capacity %lld", (long long)h[0], (long long)capacity);
   return MGPU_OK;
 }
@@ -3619,6 +3693,108 @@ int32_t mgpu_pip_join_fetch(mgpu_ctx* ctx, int64_t capacity, int64_t* out_n_pair
   e.out_poly = out_polygon_id;
   HIP_TRY(mgpu::launch_emit(e, L.n_tiles, s));
   HIP_TRY(hipStreamSynchronize(s));
+  return MGPU_OK;
+}
+
+int32_t mgpu_chips_polygons(const mgpu_chips* chips, int32_t* out_ids, int64_t cap, int64_t* out_n) {
+  if (!chips || !out_n || cap < 0) return fail(MGPU_E_INVALID_ARG, "bad arguments");
+  const PolySlotsDev* ps = nullptr;
+  if (int32_t st = ensure_poly_slots(chips, &ps)) return st;
+  const int64_t P = (int64_t)ps->ids.size();
+  *out_n = P;
+  if (P > cap || (P > 0 && !out_ids))
+    return fail(MGPU_E_CAPACITY, "%lld polygons, capacity %lld", (long long)P, (long long)(out_ids ? cap : 0));
+  if (P) memcpy(out_ids, ps->ids.data(), (size_t)P * 4);
+  return MGPU_OK;
+}
+
+// mgpu_pip_join in count mode (join_impl: nothing that writes pairs is launched), settled
+// as the pair join is -- near-tie queue, host libm pass, override rerun -- then one
+// aggregation launch over what the join left in device memory (kernels.h CountArgs).
+// Aggregating only after settle_join keeps reruns free of un-counting, and a failing call
+// never touches count / sum.  The fused pipeline's overflow pool has no capacity to size
+// it: n records first, and one rerun with the size the first run asked for.
+int32_t mgpu_pip_join_count(mgpu_ctx* ctx, const mgpu_chips* chips, int32_t is, int32_t res, const double* x,
+                            const double* y, const int64_t* weight, int64_t n, int64_t n_slots, int64_t* count,
+                            int64_t* sum, int32_t accumulate, void* stream, mgpu_stats* stats) {
+  if (!ctx || !chips) return fail(MGPU_E_INVALID_ARG, "ctx/chips is NULL");
+  if ((weight && !sum) || (sum && !weight && n > 0))  // (an empty batch's weight column may be NULL)
+    return fail(MGPU_E_INVALID_ARG, "pip_join_count: weight and sum go together (both or neither)");
+  const PolySlotsDev* ps = nullptr;
+  if (int32_t st = ensure_poly_slots(chips, &ps)) return st;
+  const int64_t P = (int64_t)ps->ids.size();
+  if (n_slots != P)
+    return fail(MGPU_E_INVALID_ARG, "pip_join_count: n_slots %lld, the chip table has %lld polygons", (long long)n_slots,
+                (long long)P);
+  if (P > 0 && !count) return fail(MGPU_E_INVALID_ARG, "pip_join_count: count is NULL");
+  const hipStream_t s = (hipStream_t)stream;
+  JoinCall c{chips, is, res, x, y, nullptr, 0, n, 0, nullptr, nullptr, s, nullptr, 0, nullptr, std::max<int64_t>(n, 0)};
+  const bool reference_libm = is == MGPU_H3 && ctx->opt.h3_libm == MGPU_LIBM_REFERENCE;
+  int64_t pairs = 0;
+  if (int32_t st = launch_call(ctx, c, true, 0, reference_libm)) return st;
+  if (int32_t st = settle_join(ctx, c, true, reference_libm, &pairs, stats)) return st;
+  auto& L = ctx->last;
+  if (!L.pool_ok) {
+    c.count_pool = L.pool_used;
+    if (int32_t st = launch_call(ctx, c, true, 0, reference_libm)) return st;
+    if (int32_t st = settle_join(ctx, c, true, reference_libm, &pairs, stats)) return st;
+    if (!L.pool_ok)
+      return fail(MGPU_E_INTERNAL, "pip_join_count: the overflow pool of %lld records is short again (%lld asked for)",
+                  (long long)L.pool, (long long)L.pool_used);
+  }
+  mgpu::CountArgs ca{};
+  ca.ids = ps->d_ids;
+  ca.n_slots = (uint32_t)P;
+  ca.chip_slot = ps->d_chip_slot;
+  ca.dense = ps->d_dense;
+  ca.min_id = P ? ps->ids.front() : 0;
+  ca.contiguous = (P > 0 && (int64_t)ps->ids.back() - ps->ids.front() + 1 == P) ? 1u : 0u;
+  // LDS histograms hold u32 counts: only while no slot of a workgroup can pass 2^32
+  ca.lds_slots = (P > 0 && P <= ctx->opt.count_lds_slots && pairs < ((int64_t)1 << 32)) ? (uint32_t)P : 0u;
+  // more polygons than LDS slots: an LDS hash table per workgroup in front of the global
+  // atomics (device-scope atomics run at the memory side: C3's 1.25e8 took 6.7 ms)
+  ca.hash_slots = (!ca.lds_slots && ctx->opt.count_lds_slots > 0 && P > 0 && pairs < ((int64_t)1 << 32))
+                      ? mgpu::kCountHash : 0u;
+  const int64_t look_n = ca.dense ? (int64_t)ps->ids.back() - ps->ids.front() + 1 : P;
+  ca.stage_n = (look_n <= mgpu::kCountStageMax && !ca.hash_slots && !ca.contiguous) ? (uint32_t)look_n : 0u;
+  ca.weight = weight;
+  ca.count = (unsigned long long*)count;
+  ca.sum = (unsigned long long*)sum;
+  ca.dropped = (uint32_t*)((unsigned long long*)ctx->ws + kWsCountDropped);
+  if (!accumulate && P > 0) {
+    HIP_TRY(hipMemsetAsync(count, 0, (size_t)P * 8, s));
+    if (sum) HIP_TRY(hipMemsetAsync(sum, 0, (size_t)P * 8, s));
+  }
+  HIP_TRY(hipEventRecord(ctx->ev2, s));
+  if (L.split)
+    HIP_TRY(mgpu::launch_split_count(is, L.sargs, ca, s));
+  else if (L.binned)
+    HIP_TRY(mgpu::launch_bin_count(L.bargs, ca, s));
+  else
+    HIP_TRY(mgpu::launch_tile_count(L.emit, L.n_tiles, ca, s));
+  HIP_TRY(hipEventRecord(ctx->ev3, s));
+  HIP_TRY(hipMemcpyAsync(ctx->pin, ca.dropped, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(stream_wait(ctx, s));
+  if (ctx->pin[0]) return fail(MGPU_E_INTERNAL, "pip_join_count: a tile's records were dropped by the overflow pool");
+  if (stats) {
+    float ms = 0;
+    hipEventElapsedTime(&ms, ctx->ev2, ctx->ev3);
+    stats->emit_kernel_ms = ms;
+    stats->kernel_ms += ms;
+  }
+  return MGPU_OK;
+}
+
+int32_t mgpu_test_poly_slots_host(const int32_t* polygon_id, int64_t n, int32_t* out_ids, int64_t* out_n,
+                                  uint32_t* out_slot_of_row) {
+  if (n < 0 || !out_n || (n > 0 && (!polygon_id || !out_ids || !out_slot_of_row)))
+    return fail(MGPU_E_INVALID_ARG, "bad arguments");
+  const mgpu::PolySlots hs = mgpu::poly_slots(polygon_id, n);
+  *out_n = (int64_t)hs.ids.size();
+  if (n) {
+    memcpy(out_ids, hs.ids.data(), hs.ids.size() * 4);
+    memcpy(out_slot_of_row, hs.slot_of_row.data(), (size_t)n * 4);
+  }
   return MGPU_OK;
 }
 

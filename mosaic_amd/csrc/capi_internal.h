@@ -19,6 +19,7 @@ struct mgpu_options {
   int64_t bin_keys = 0;                   // ... H3: grid keys computed by the scatter kernel (A/B r5: slower)
   int64_t spin_us = 2000;                 // synchronous calls: poll (yielding) this long, then block
   int64_t ring_batch = (int64_t)1 << 26;   // ring joins: candidate pairs held in scratch at a time
+  int64_t count_lds_slots = 4096;         // mgpu_pip_join_count: LDS histograms up to this many polygons (kernels.h kCountLdsSlotsMax)
   int64_t bng_split = 0;                  // BNG dense tables: the split pipeline, the grid entry as the code (A/B r6: C4 2.43 vs 2.17 ms fused -- off)
   // the chip-table builder of mgpu_chips_upload on this context (mgpu_build_opts)
   int64_t raster = 1, raster_bng = 0, raster_sub = 16, raster_milli = 250;
@@ -80,6 +81,9 @@ struct mgpu_ctx {
     int64_t capacity = 0;
     int64_t* out_point = nullptr;
     int32_t* out_poly = nullptr;
+    // the fused pipeline's overflow pool of that join and the records it asked for
+    // (mgpu_pip_join: the capacity; mgpu_pip_join_count: n, or the size a first run reported)
+    int64_t pool = 0, pool_used = 0;
   } last;
 };
 
@@ -90,6 +94,9 @@ struct mgpu_chips {
   size_t bytes = 0;
   mgpu::ChipTableView view{};
   int64_t n_vertices = 0;
+  // mgpu_pip_join_count's id -> slot table (capi.cpp PolySlotsDev), built at the first use
+  // from chip_poly and kept outside the blob
+  mutable void* slots = nullptr;
 };
 
 namespace mgpu {

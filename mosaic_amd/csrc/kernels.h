@@ -105,10 +105,13 @@ struct SplitArgs {
 int64_t split_chunk();
 int64_t split_chunk_tiles();
 int64_t split_chunks(int64_t n);
-hipError_t launch_split(int is, const SplitArgs& a, hipStream_t s, hipEvent_t after_classify, hipEvent_t after_mixed);
+// emit = false (mgpu_pip_join_count): everything but split_emit_kernel -- the scan stays, it yields counters[0]
+hipError_t launch_split(int is, const SplitArgs& a, hipStream_t s, hipEvent_t after_classify, hipEvent_t after_mixed,
+                        bool emit = true);
 hipError_t launch_split_emit(int is, const SplitArgs& a, hipStream_t s);
 // the override passes (kernels.hip launch_join_redo): the split pipeline's over R.list's n chunks
-hipError_t launch_split_redo(int is, const SplitArgs& sa, const RedoArgs& R, int64_t n, hipStream_t s);
+hipError_t launch_split_redo(int is, const SplitArgs& sa, const RedoArgs& R, int64_t n, hipStream_t s,
+                             bool emit = true);
 
 // The binned pipeline (a chip table far larger than the caches): the points
 // are counting-sorted by a coarse spatial bin so that the join walks the chip table bin
@@ -146,7 +149,8 @@ int64_t bin_chunk();
 int64_t bin_chunks(int64_t n);
 int64_t bin_groups(int64_t n);
 int32_t bin_max();
-hipError_t launch_binned(int is, const BinArgs& a, hipStream_t s, hipEvent_t after_bin, hipEvent_t after_join);
+hipError_t launch_binned(int is, const BinArgs& a, hipStream_t s, hipEvent_t after_bin, hipEvent_t after_join,
+                         bool emit = true);
 hipError_t launch_bin_emit(const BinArgs& a, hipStream_t s);
 
 // pair_emit_kernel: tile records -> ordered (point_id, polygon_id) output
@@ -198,11 +202,40 @@ int64_t join_tiles(int64_t n);
 int64_t join_tile_points();
 int64_t join_slot_records();   // records reserved per tile (pairs beyond go to the overflow pool)
 // `after_stream` (optional) is recorded right after pip_join_kernel
-hipError_t launch_join(int is, const JoinArgs& a, const EmitArgs& e, hipStream_t s, hipEvent_t after_stream);
+hipError_t launch_join(int is, const JoinArgs& a, const EmitArgs& e, hipStream_t s, hipEvent_t after_stream,
+                       bool emit = true);
 // ... and the fused join's over R.list's n tiles
-hipError_t launch_join_redo(int is, const JoinArgs& a, const EmitArgs& e, const RedoArgs& R, int64_t n, hipStream_t s);
+hipError_t launch_join_redo(int is, const JoinArgs& a, const EmitArgs& e, const RedoArgs& R, int64_t n, hipStream_t s,
+                            bool emit = true);
 // pair_emit_kernel alone, over the records a join left in the workspace
 hipError_t launch_emit(const EmitArgs& e, int64_t n_tiles, hipStream_t s);
+
+// mgpu_pip_join_count's aggregation (count_kernels.inc): per polygon slot -- the table's
+// distinct polygon ids ascending -- the pairs a finished join left in device memory, and
+// the sum of their points' weights.  One launch per pipeline, over what that pipeline's
+// emit kernel reads.
+struct CountArgs {
+  const int32_t* ids;           // [n_slots] the distinct polygon ids, ascending
+  uint32_t n_slots;
+  const uint32_t* chip_slot;    // [n_chips] slot of chip_poly[i]
+  const uint32_t* dense;        // [max id - min id + 1] id - min_id -> slot, or null (binary search of ids)
+  int32_t min_id;
+  uint32_t contiguous;          // the ids are min_id .. min_id + n_slots - 1: slot = id - min_id, no lookup
+  uint32_t lds_slots;           // n_slots: per-workgroup LDS histograms; 0: none
+  uint32_t hash_slots;          // (lds_slots == 0) kCountHash: a per-workgroup LDS hash table of the slots
+                                // it meets, the rest by global atomics; 0: global atomics only
+  uint32_t stage_n;             // > 0: the lookup reads an LDS copy of the dense table (its size) / of ids (n_slots)
+  const int64_t* weight;        // [n] per input point, or null (then sum is null)
+  unsigned long long* count;    // [n_slots] added to
+  unsigned long long* sum;      // [n_slots] added to (two's complement wrap)
+  uint32_t* dropped;            // set when a fused tile's records were dropped by the overflow pool
+};
+constexpr int64_t kCountLdsSlotsMax = 4096;  // 48 KiB of u32 counts + u64 sums per workgroup
+constexpr uint32_t kCountHash = 4096;        // hash entries (tag, u32 count, u64 sum): 64 KiB weighted
+constexpr int64_t kCountStageMax = 2048;     // lookup entries (dense table or sorted ids) staged in LDS (8 KiB)
+hipError_t launch_split_count(int is, const SplitArgs& a, const CountArgs& c, hipStream_t s);
+hipError_t launch_tile_count(const EmitArgs& e, int64_t n_tiles, const CountArgs& c, hipStream_t s);
+hipError_t launch_bin_count(const BinArgs& b, const CountArgs& c, hipStream_t s);
 // StringType cell ids: offsets[n + 1] (device); chunk: scratch of format_chunks(n) int64;
 // counters[2] += ids without a string form (BNG)
 int64_t format_chunks(int64_t n);

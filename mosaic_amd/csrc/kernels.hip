@@ -19,6 +19,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <map>
+#include <mutex>
+
 #define H3T_QUAL static __constant__ const
 #include "h3_core.h"
 #include "bng_core.h"
@@ -2955,7 +2958,7 @@ int64_t join_slot_records() { return kSlot; }
 #define MGPU_FIX_GRID 8192
 #endif
 constexpr int64_t kFixGrid = MGPU_FIX_GRID;  // fix-kernel workgroups (one wave each; idle ones exit at once)
-hipError_t launch_join(int is, const JoinArgs& a, const EmitArgs& e, hipStream_t s, hipEvent_t after_stream) {
+hipError_t launch_join(int is, const JoinArgs& a, const EmitArgs& e, hipStream_t s, hipEvent_t after_stream, bool emit) {
   if (a.n_tiles <= 0) return hipSuccess;
   // BNG has no near-ties, but its tiles still go dirty on a cell of more than 32
   // chips, a candidate-list overflow or a chip without a strip index
@@ -2973,8 +2976,9 @@ hipError_t launch_join(int is, const JoinArgs& a, const EmitArgs& e, hipStream_t
   }
   hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(kScanBlock), 0, s, a.group_sum, a.group_cand,
                      (a.n_tiles + kScanGroup - 1) / kScanGroup, e.group_off, a.counters);
-  hipLaunchKernelGGL(pair_emit_kernel, dim3((unsigned)((a.n_tiles + kEmitTiles - 1) / kEmitTiles)),
-                     dim3(kEmitBlock), 0, s, e, a.n_tiles);
+  if (emit)
+    hipLaunchKernelGGL(pair_emit_kernel, dim3((unsigned)((a.n_tiles + kEmitTiles - 1) / kEmitTiles)),
+                       dim3(kEmitBlock), 0, s, e, a.n_tiles);
   return hipGetLastError();
 }
 
@@ -3026,7 +3030,8 @@ __global__ __launch_bounds__(256) void redo_compare_kernel(const uint32_t* count
   }
 }
 
-hipError_t launch_join_redo(int is, const JoinArgs& a, const EmitArgs& e, const RedoArgs& R, int64_t n, hipStream_t s) {
+hipError_t launch_join_redo(int is, const JoinArgs& a, const EmitArgs& e, const RedoArgs& R, int64_t n, hipStream_t s,
+                            bool emit) {
   if (n <= 0) return hipSuccess;
   const unsigned g = (unsigned)((n + 255) / 256);
   hipLaunchKernelGGL(tile_unpair_kernel, dim3(g), dim3(256), 0, s, a, R, n);
@@ -3041,8 +3046,9 @@ hipError_t launch_join_redo(int is, const JoinArgs& a, const EmitArgs& e, const 
   EmitArgs er = e;
   er.redo_first = R.first;
   er.redo_affected = R.affected;
-  hipLaunchKernelGGL(pair_emit_kernel, dim3((unsigned)((a.n_tiles + kEmitTiles - 1) / kEmitTiles)),
-                     dim3(kEmitBlock), 0, s, er, a.n_tiles);
+  if (emit)
+    hipLaunchKernelGGL(pair_emit_kernel, dim3((unsigned)((a.n_tiles + kEmitTiles - 1) / kEmitTiles)),
+                       dim3(kEmitBlock), 0, s, er, a.n_tiles);
   return hipGetLastError();
 }
 
@@ -3068,7 +3074,7 @@ static void launch_emit(const SplitArgs& a, int64_t nc, hipStream_t s) {
 }
 
 template <int IS>
-static void launch_split_t(const SplitArgs& a, hipStream_t s, hipEvent_t after_classify, hipEvent_t after_mixed) {
+static void launch_split_t(const SplitArgs& a, hipStream_t s, hipEvent_t after_classify, hipEvent_t after_mixed, bool emit) {
   const int64_t nc = split_chunks(a.j.n);
   const ChipTableView& ct = a.j.chips;
   const size_t nblk = (IS == MGPU_H3 && ct.raster_blk) ? (size_t)ct.raster_bnx * ct.raster_bny : 0;
@@ -3096,20 +3102,21 @@ static void launch_split_t(const SplitArgs& a, hipStream_t s, hipEvent_t after_c
   if (after_mixed) hipEventRecord(after_mixed, s);
   hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(kScanBlock), 0, s, a.chunk_pairs, a.j.group_cand, nc,
                      a.chunk_off, a.j.counters);
-  launch_emit<IS>(a, nc, s);
+  if (emit) launch_emit<IS>(a, nc, s);
 }
 
-hipError_t launch_split(int is, const SplitArgs& a, hipStream_t s, hipEvent_t after_classify, hipEvent_t after_mixed) {
+hipError_t launch_split(int is, const SplitArgs& a, hipStream_t s, hipEvent_t after_classify, hipEvent_t after_mixed,
+                        bool emit) {
   if (a.j.n <= 0) return hipSuccess;
   if (is == MGPU_H3)
-    launch_split_t<MGPU_H3>(a, s, after_classify, after_mixed);
+    launch_split_t<MGPU_H3>(a, s, after_classify, after_mixed, emit);
   else
-    launch_split_t<MGPU_BNG>(a, s, after_classify, after_mixed);
+    launch_split_t<MGPU_BNG>(a, s, after_classify, after_mixed, emit);
   return hipGetLastError();
 }
 
 // the split pipeline's override pass (launch_join_redo): R.list = the chunks, n of them
-hipError_t launch_split_redo(int is, const SplitArgs& sa, const RedoArgs& R, int64_t n, hipStream_t s) {
+hipError_t launch_split_redo(int is, const SplitArgs& sa, const RedoArgs& R, int64_t n, hipStream_t s, bool emit) {
   if (n <= 0) return hipSuccess;
   const int64_t nc = split_chunks(sa.j.n);
   hipLaunchKernelGGL(chunk_unpair_kernel, dim3((unsigned)n), dim3(256), 0, s, sa.j, R);
@@ -3126,6 +3133,7 @@ hipError_t launch_split_redo(int is, const SplitArgs& sa, const RedoArgs& R, int
   SplitArgs sr = sa;
   sr.redo_first = R.first;
   sr.redo_affected = R.affected;
+  if (!emit) return hipGetLastError();
   if (is == MGPU_H3)
     launch_emit<MGPU_H3>(sr, nc, s);
   else
@@ -3154,12 +3162,13 @@ int32_t bin_max() { return kBinMax; }
 // (A/B r5, profiles/r5/ab_c3_fused_output.txt: the three in one resident-grid pass with
 // a decoupled look-back over the chunks took 11.1 ms instead of 1.0 on C3 -- a chunk's
 // look-back walks back through the whole grid's round one dependent load at a time)
-static void launch_bin_output(const BinArgs& a, hipStream_t s) {
+static void launch_bin_output(const BinArgs& a, hipStream_t s, bool emit) {
   const int64_t n = a.s.j.n, K = bin_chunks(n), nc = split_chunks(n);
   if (!MGPU_BIN_JOIN_COUNTS)
     hipLaunchKernelGGL(bin_gather_kernel, dim3((unsigned)K), dim3(kBinBlock), 0, s, a);
   hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(kScanBlock), 0, s, a.s.chunk_pairs, a.s.j.group_cand, nc,
                      a.s.chunk_off, a.s.j.counters);
+  if (!emit) return;
   if (MGPU_BIN_JOIN_COUNTS)
     hipLaunchKernelGGL(bin_emit_gather_kernel, dim3((unsigned)K), dim3(kBinBlock), 0, s, a);
   else
@@ -3167,7 +3176,7 @@ static void launch_bin_output(const BinArgs& a, hipStream_t s) {
 }
 
 template <int IS>
-static void launch_binned_t(const BinArgs& a, hipStream_t s, hipEvent_t after_bin, hipEvent_t after_join) {
+static void launch_binned_t(const BinArgs& a, hipStream_t s, hipEvent_t after_bin, hipEvent_t after_join, bool emit) {
   const int64_t n = a.s.j.n, K = bin_chunks(n), G = bin_groups(n), nb = (int64_t)a.nbx * a.nby;
   hipLaunchKernelGGL(bin_hist_kernel, dim3((unsigned)K), dim3(kBinBlock), 0, s, a);
   hipLaunchKernelGGL(bin_colscan_kernel, dim3((unsigned)((nb + 255) / 256), (unsigned)G), dim3(256), 0, s, a, K);
@@ -3192,16 +3201,17 @@ static void launch_binned_t(const BinArgs& a, hipStream_t s, hipEvent_t after_bi
   if (after_join) hipEventRecord(after_join, s);
   const int64_t fix = tiles < kFixGrid ? tiles : kFixGrid;
   hipLaunchKernelGGL((pip_mixed_fix_kernel<IS, 1>), dim3((unsigned)fix), dim3(kBlock), 0, s, j);
-  launch_bin_output(a, s);
+  launch_bin_output(a, s, emit);
 }
 
-hipError_t launch_binned(int is, const BinArgs& a, hipStream_t s, hipEvent_t after_bin, hipEvent_t after_join) {
+hipError_t launch_binned(int is, const BinArgs& a, hipStream_t s, hipEvent_t after_bin, hipEvent_t after_join,
+                         bool emit) {
   if (a.s.j.n <= 0) return hipSuccess;
   if (a.nbx < 1 || a.nby < 1 || (int64_t)a.nbx * a.nby > kBinMax) return hipErrorInvalidValue;
   if (is == MGPU_H3)
-    launch_binned_t<MGPU_H3>(a, s, after_bin, after_join);
+    launch_binned_t<MGPU_H3>(a, s, after_bin, after_join, emit);
   else
-    launch_binned_t<MGPU_BNG>(a, s, after_bin, after_join);
+    launch_binned_t<MGPU_BNG>(a, s, after_bin, after_join, emit);
   return hipGetLastError();
 }
 
@@ -3229,5 +3239,7 @@ hipError_t launch_st_contains(const ChipTableView& t, const int64_t* row, const 
                      y, n, out, counters);
   return hipGetLastError();
 }
+
+#include "count_kernels.inc"
 
 }  // namespace mgpu

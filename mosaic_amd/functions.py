@@ -277,6 +277,74 @@ def pip_join(x, y, chips, resolution, index_system=None, point_id=None, point_id
     return JoinResult(op[:m], oq[:m], st.as_dict())
 
 
+class CountResult:
+    """pip_join_count's result: ``polygon_id`` (int32 tensor, the table's distinct ids
+    ascending), ``count`` (int64 tensor, pairs per polygon), ``sum`` (int64 tensor, the
+    weights summed per polygon, or None without a weight) and the stats dict."""
+
+    def __init__(self, polygon_id, count, sum, stats):
+        self.polygon_id = polygon_id
+        self.count = count
+        self.sum = sum
+        self.stats = stats
+
+    def __len__(self):
+        return self.polygon_id.numel()
+
+
+def pip_join_count(x, y, chips, resolution, index_system=None, weight=None, out=None, accumulate=False, stream=None):
+    """The join aggregated per polygon (mgpu_pip_join_count): for the table's distinct
+    polygon ids ascending, the number of pairs pip_join emits for the same inputs and --
+    with ``weight``, an int64 device column of one value per point -- the sum of the
+    weights over those pairs (two's complement wrap).  No pairs are written.
+
+    ``out`` = (count, sum) preallocated int64 device tensors of one element per polygon
+    (sum None without a weight); ``accumulate`` adds to their contents instead of
+    overwriting them, so a stream of batches is one call each into the same arrays.  A
+    call that raises leaves them untouched."""
+    import ctypes
+    import torch
+    isys = index_system or _H3
+    res = isys.get_resolution(resolution)
+    if isinstance(chips, ChipTable):
+        if chips.index_system != isys.code:
+            raise N.IllegalArgumentException(N.MGPU_E_INVALID_ARG, "chip table built for another index system")
+        chips = chips.upload()
+    _check_points(x, y)
+    n = x.numel()
+    if chips.ctx.device != x.device:
+        raise N.IllegalArgumentException(N.MGPU_E_INVALID_ARG, "chip table on %s, points on %s" % (chips.ctx.device, x.device))
+    w_ptr = None
+    if weight is not None:
+        if weight.dtype != torch.int64 or weight.numel() != n or weight.device != x.device:
+            raise N.IllegalArgumentException(N.MGPU_E_INVALID_ARG, "weight must be int64 on the points' device, one value per point")
+        weight = weight.contiguous()  # kept alive (bound here) until the call returns
+        w_ptr = weight.data_ptr()
+    ids = chips.polygons()
+    if out is not None:
+        cnt, sm = out
+        for t, what in ((cnt, "count"), (sm, "sum")):
+            if t is not None and (t.dtype != torch.int64 or t.device != x.device or not t.is_contiguous()):
+                raise N.IllegalArgumentException(N.MGPU_E_INVALID_ARG, "out %s must be a contiguous int64 tensor on the points' device" % what)
+        if cnt is None or (sm is None) != (weight is None):
+            raise N.IllegalArgumentException(N.MGPU_E_INVALID_ARG, "out must be (count, sum), sum None exactly when weight is None")
+        if sm is not None and sm.numel() != cnt.numel():
+            raise N.IllegalArgumentException(N.MGPU_E_INVALID_ARG, "out count and sum differ in length")
+        n_slots = cnt.numel()
+    else:
+        if accumulate:
+            raise N.IllegalArgumentException(N.MGPU_E_INVALID_ARG, "accumulate needs out=(count, sum) to add to")
+        n_slots = len(ids)
+        cnt = torch.empty(n_slots, dtype=torch.int64, device=x.device)
+        sm = torch.empty(n_slots, dtype=torch.int64, device=x.device) if weight is not None else None
+    s = stream if stream is not None else torch.cuda.current_stream(x.device).cuda_stream
+    st = N.MgpuStats()
+    N.check(N.lib().mgpu_pip_join_count(chips.ctx.handle, chips.handle, isys.code, res, x.data_ptr(), y.data_ptr(),
+                                        w_ptr, n, n_slots, cnt.data_ptr(), None if sm is None else sm.data_ptr(),
+                                        1 if accumulate else 0, s, ctypes.byref(st)))
+    return CountResult(chips.polygons_device(), cnt, sm, st.as_dict())
+
+
 class AsyncJoin:
     """A join enqueued by pip_join_async: ``finish()`` settles it (mgpu_pip_join_finish:
     the stream's wait, the H3 near-ties recomputed with the reference's libm, a rerun only
