@@ -122,6 +122,9 @@ int32_t mgpu_ctx_destroy(mgpu_ctx* ctx);
  *                     counts and sums per workgroup, two workgroups per CU); larger tables go through a
  *                     per-workgroup LDS hash table in front of global atomics; 0: every
  *                     addition is a global atomic
+ *   "count_groups"    0 (default): mgpu_pip_join_count's aggregation kernel runs on its
+ *                     resident grid; 1..65536: on at most this many workgroups (a test hook:
+ *                     a small value makes every workgroup take many chunks or tiles)
  *   "raster", "raster_bng", "raster_sub", "raster_milli"
  *                     the chip-table builder of mgpu_chips_upload on this context
  *                     (mgpu_build_opts below)
@@ -242,6 +245,10 @@ int32_t mgpu_chips_destroy(mgpu_chips* chips);
 int32_t mgpu_chips_device_blob(const mgpu_chips* chips, void** device_ptr, int64_t* bytes);
 int32_t mgpu_chips_from_device_blob(mgpu_ctx* ctx, const void* device_ptr, int64_t bytes, mgpu_chips** out);
 int32_t mgpu_chips_info(const mgpu_chips* chips, int64_t* n_chips, int64_t* n_cells, int64_t* n_vertices);
+/* The table's pixel index (no reference counterpart; read-only): *mode = 0 when it has
+ * none, *n_classes = the pixel classes of an H3 table's index, class 0 (empty) included
+ * (else 0).  Either may be NULL. */
+int32_t mgpu_chips_raster_info(const mgpu_chips* chips, int64_t* mode, int64_t* n_classes);
 /* The distinct polygon ids of the table, ascending, into out_ids[cap] (host); *out_n =
  * their number P.  These are the slots of mgpu_pip_join_count: slot k is out_ids[k].
  * MGPU_E_CAPACITY with *out_n set if cap is short (cap 0 / out_ids NULL asks for P).  The

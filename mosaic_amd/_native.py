@@ -44,7 +44,7 @@ EXPORTS = (
     "mgpu_test_h3_glibc_host", "mgpu_internal_geometry_to_cells", "mgpu_test_internal_centroid", "mgpu_test_join_counters",
     "mgpu_test_receive_blob", "mgpu_ring_join", "mgpu_ring_join_ex", "mgpu_ring_join_final",
     "mgpu_test_overlay_verify",
-    "mgpu_chips_polygons", "mgpu_pip_join_count", "mgpu_test_poly_slots_host",
+    "mgpu_chips_polygons", "mgpu_pip_join_count", "mgpu_test_poly_slots_host", "mgpu_chips_raster_info",
 )
 MGPU_GEOM_WKB = 0
 MGPU_GEOM_WKT = 1
@@ -131,6 +131,7 @@ def lib():
         "mgpu_chips_device_blob": (I32, [P, ctypes.POINTER(P), ctypes.POINTER(I64)]),
         "mgpu_chips_from_device_blob": (I32, [P, P, I64, ctypes.POINTER(P)]),
         "mgpu_chips_info": (I32, [P, ctypes.POINTER(I64), ctypes.POINTER(I64), ctypes.POINTER(I64)]),
+        "mgpu_chips_raster_info": (I32, [P, ctypes.POINTER(I64), ctypes.POINTER(I64)]),
         "mgpu_st_contains": (I32, [P, P, P, P, P, I64, P, P]),
         "mgpu_pip_join": (I32, [P, P, I32, I32, P, P, P, I64, I64, I64, ctypes.POINTER(I64), P, P, P,
                                 ctypes.POINTER(MgpuStats)]),

@@ -86,7 +86,10 @@ class DeviceChips:
         a, b, c = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
         N.check(N.lib().mgpu_chips_info(self.handle, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
         p, n = self.device_blob()
-        return {"chips": a.value, "cells": b.value, "vertices": c.value, "bytes": n}
+        m, k = ctypes.c_int64(), ctypes.c_int64()
+        N.check(N.lib().mgpu_chips_raster_info(self.handle, ctypes.byref(m), ctypes.byref(k)))
+        return {"chips": a.value, "cells": b.value, "vertices": c.value, "bytes": n, "raster_mode": m.value,
+                "raster_ncls": k.value}
 
     def polygons(self):
         """The table's distinct polygon ids, ascending (int32 numpy array; mgpu_chips_polygons):

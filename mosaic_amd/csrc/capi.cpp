@@ -1876,6 +1876,9 @@ int32_t mgpu_ctx_set_option(mgpu_ctx* ctx, const char* key, int64_t v) {
   } else if (k == "count_lds_slots") {
     if (v < 0 || v > mgpu::kCountLdsSlotsMax) return bad();
     o.count_lds_slots = v;
+  } else if (k == "count_groups") {
+    if (v < 0 || v > mgpu::kCountGroupsMax) return bad();
+    o.count_groups = v;
   } else if (k == "spin_us") {
     if (v < 0 || v > 10000000) return bad();
     o.spin_us = v;
@@ -1901,7 +1904,7 @@ int32_t mgpu_ctx_get_option(const mgpu_ctx* ctx, const char* key, int64_t* v) {
       {"h3_libm", o.h3_libm},       {"pipeline", o.pipeline}, {"bin_count", o.bin_count},
       {"bin_min_mb", o.bin_min_mb}, {"bin_min_points", o.bin_min_points}, {"bin_xcd", o.bin_xcd},
       {"bin_keys", o.bin_keys},     {"spin_us", o.spin_us},   {"ring_batch", o.ring_batch},       {"raster", o.raster},     {"raster_bng", o.raster_bng},
-      {"bng_split", o.bng_split},   {"count_lds_slots", o.count_lds_slots},
+      {"bng_split", o.bng_split},   {"count_lds_slots", o.count_lds_slots}, {"count_groups", o.count_groups},
       {"raster_sub", o.raster_sub}, {"raster_milli", o.raster_milli}};
   for (const auto& kv : all)
     if (strcmp(kv.first, key) == 0) {
@@ -3067,6 +3070,13 @@ int32_t mgpu_chips_info(const mgpu_chips* chips, int64_t* n_chips, int64_t* n_ce
   return MGPU_OK;
 }
 
+int32_t mgpu_chips_raster_info(const mgpu_chips* chips, int64_t* mode, int64_t* n_classes) {
+  if (!chips) return fail(MGPU_E_INVALID_ARG, "chips is NULL");
+  if (mode) *mode = chips->view.raster_mode;
+  if (n_classes) *n_classes = chips->view.raster_mode != mgpu::kRasterNone ? (int64_t)chips->view.raster_ncls : 0;
+  return MGPU_OK;
+}
+
 int32_t mgpu_chips_device_blob(const mgpu_chips* chips, void** device_ptr, int64_t* bytes) {
   if (!chips || !device_ptr || !bytes) return fail(MGPU_E_INVALID_ARG, "NULL argument");
   *device_ptr = chips->blob;
@@ -3757,6 +3767,7 @@ int32_t mgpu_pip_join_count(mgpu_ctx* ctx, const mgpu_chips* chips, int32_t is, 
                       ? mgpu::kCountHash : 0u;
   const int64_t look_n = ca.dense ? (int64_t)ps->ids.back() - ps->ids.front() + 1 : P;
   ca.stage_n = (look_n <= mgpu::kCountStageMax && !ca.hash_slots && !ca.contiguous) ? (uint32_t)look_n : 0u;
+  ca.max_groups = (uint32_t)ctx->opt.count_groups;
   ca.weight = weight;
   ca.count = (unsigned long long*)count;
   ca.sum = (unsigned long long*)sum;

@@ -468,7 +468,8 @@ static hipError_t launch_count_grid(K kernel, int block, int64_t units, const Co
   }
   const int64_t by_lds = (160 * 1024) / (int64_t)(lds + 8192), by_waves = 32 / (block / 64);
   const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(8, std::min(by_lds, by_waves)));
-  const int64_t grid = std::min<int64_t>(units, per_cu * cus);
+  int64_t grid = std::min<int64_t>(units, per_cu * cus);
+  if (c.max_groups) grid = std::min<int64_t>(grid, c.max_groups);  // (option count_groups: the stride loops under test)
   hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(block), lds, s, args...);
   return hipSuccess;
 }

@@ -229,8 +229,10 @@ struct CountArgs {
   unsigned long long* count;    // [n_slots] added to
   unsigned long long* sum;      // [n_slots] added to (two's complement wrap)
   uint32_t* dropped;            // set when a fused tile's records were dropped by the overflow pool
+  uint32_t max_groups;          // host only (option count_groups): at most this many workgroups; 0: the resident grid
 };
 constexpr int64_t kCountLdsSlotsMax = 4096;  // 48 KiB of u32 counts + u64 sums per workgroup
+constexpr int64_t kCountGroupsMax = 65536;   // option count_groups
 constexpr uint32_t kCountHash = 4096;        // hash entries (tag, u32 count, u64 sum): 64 KiB weighted
 constexpr int64_t kCountStageMax = 2048;     // lookup entries (dense table or sorted ids) staged in LDS (8 KiB)
 hipError_t launch_split_count(int is, const SplitArgs& a, const CountArgs& c, hipStream_t s);
