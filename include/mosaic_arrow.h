@@ -70,7 +70,10 @@ struct ArrowDeviceArray {
  * the context's device): x, y float64 (format "g"), optional point_id int64 ("l", no
  * nulls; NULL = offset + row index).  Array offsets are honoured; a null x or y (validity
  * bitmaps) is a null point, which matches nothing (NullIntolerant: no pair), as in the
- * reference.  If an array carries a sync_event (a hipEvent_t) the work waits on it.
+ * reference.  An array whose null_count is 0 has no nulls: its validity buffer, if it
+ * carries one, is not read (Arrow lets that buffer be NULL then); any other null_count,
+ * -1 ("not computed") included, makes the bitmap decide.  The same holds for the geometry
+ * column below.  If an array carries a sync_event (a hipEvent_t) the work waits on it.
  * Otherwise as mgpu_pip_join. */
 int32_t mgpu_pip_join_arrow(mgpu_ctx* ctx, const mgpu_chips* chips, int32_t index_system, int32_t res,
                             const struct ArrowDeviceArray* x, const struct ArrowDeviceArray* y,

@@ -64,12 +64,17 @@ def bitmap(present, device):
     return torch.from_numpy(np.packbits(np.asarray(present, bool), bitorder="little").copy()).to(device)
 
 
-def float64_column(values, present=None, offset=0):
+def float64_column(values, present=None, offset=0, length=None, null_count=None):
     """float64 device tensor (+ optional bool validity of the same length) -> column of
-    length values.numel() - offset starting at ``offset``."""
-    n = values.numel() - offset
+    ``length`` rows (default: values.numel() - offset) starting at ``offset``.  The null
+    count is that of the rows [offset, offset + length); ``null_count`` overrides it (-1:
+    Arrow's "not computed", which makes the callee read the bitmap)."""
+    n = values.numel() - offset if length is None else int(length)
     vb = None if present is None else bitmap(present, values.device)
-    nulls = 0 if present is None else int((~np.asarray(present, bool)[offset:]).sum())
+    if null_count is not None:
+        nulls = int(null_count)
+    else:
+        nulls = 0 if present is None else int((~np.asarray(present, bool)[offset:offset + n]).sum())
     return DeviceColumn(n, [vb, values], offset=offset, null_count=nulls, device_index=values.device.index or 0)
 
 
@@ -95,18 +100,41 @@ def pip_join_arrow(x_col, y_col, chips, resolution, index_system=None, point_id_
     return JoinResult(op[:m], oq[:m], st.as_dict())
 
 
-def geometry_column(col, large=True):
-    """functions.GeometryColumn -> Arrow binary / utf8 column (+ its schema format)."""
+def pip_join_fetch(ctx, count, stream=None):
+    """mgpu_pip_join_fetch: the pairs of the context's last join (its count as a
+    CapacityError reported it) in arrays of that size.  Returns (point ids, polygon ids)."""
+    import torch
+    op = torch.empty(max(int(count), 1), dtype=torch.int64, device=ctx.device)
+    oq = torch.empty(max(int(count), 1), dtype=torch.int32, device=ctx.device)
+    cnt = ctypes.c_int64()
+    s = stream if stream is not None else torch.cuda.current_stream(ctx.device).cuda_stream
+    N.check(N.lib().mgpu_pip_join_fetch(ctx.handle, int(count), ctypes.byref(cnt), op.data_ptr(), oq.data_ptr(), s),
+            required=cnt.value)
+    return op[:cnt.value], oq[:cnt.value]
+
+
+def geometry_column(col, large=True, offset=0, length=None):
+    """functions.GeometryColumn -> Arrow binary / utf8 column (+ its schema format) of the
+    rows [offset, offset + length) (default: to the column's end).  The buffers are the
+    whole column's: ArrowArray.offset does the slicing, of the offsets and the bitmap
+    alike (so the column's own valid_offset must be 0)."""
     import torch
     fmt = {(N.MGPU_GEOM_WKB, True): b"Z", (N.MGPU_GEOM_WKB, False): b"z",
            (N.MGPU_GEOM_WKT, True): b"U", (N.MGPU_GEOM_WKT, False): b"u"}[(col.format, large)]
     off = col.offsets if large else col.offsets.to(torch.int32)
-    n = len(col)
+    offset = int(offset)
+    n = len(col) - offset if length is None else int(length)
+    if offset < 0 or n < 0 or offset + n > len(col):
+        raise N.IllegalArgumentException(N.MGPU_E_INVALID_ARG, "slice [%d, %d) outside the column's %d rows"
+                                         % (offset, offset + n, len(col)))
     nulls = 0
     if col.valid is not None:
-        bits = np.unpackbits(col.valid.cpu().numpy(), bitorder="little")[:n]
+        if getattr(col, "valid_offset", 0):
+            raise N.IllegalArgumentException(N.MGPU_E_INVALID_ARG, "an Arrow array has one offset: valid_offset must be 0")
+        bits = np.unpackbits(col.valid.cpu().numpy(), bitorder="little")[offset:offset + n]
         nulls = int(n - bits.sum())
-    arr = DeviceColumn(n, [col.valid, off, col.data], null_count=nulls, device_index=col.data.device.index or 0)
+    arr = DeviceColumn(n, [col.valid, off, col.data], offset=offset, null_count=nulls,
+                       device_index=col.data.device.index or 0)
     schema = ArrowSchema()
     schema.format = fmt
     schema.release = _release(0)
@@ -114,21 +142,24 @@ def geometry_column(col, large=True):
     return arr, schema
 
 
-def grid_pointascellid_arrow(col, resolution, index_system=None, large=True, ctx=None, stream=None):
-    """mgpu_geometry_to_cells_arrow over a GeometryColumn handed over as an Arrow array.
-    Returns (cells int64, validity bitmap uint8)."""
+def grid_pointascellid_arrow(col, resolution, index_system=None, large=True, ctx=None, stream=None, offset=0,
+                             length=None, out_valid=None):
+    """mgpu_geometry_to_cells_arrow over a GeometryColumn handed over as an Arrow array
+    (rows [offset, offset + length) of it).  Returns (cells int64, validity bitmap uint8);
+    ``out_valid``: a caller-owned uint8 device buffer of at least (n + 7) // 8 bytes the
+    bitmap is written to (returned whole)."""
     import torch
     from .context import default_context
-    from .functions import _H3
+    from .functions import _H3, _valid_buffer
     isys = index_system or _H3
     res = isys.get_resolution(resolution)
     dev = col.data.device
     ctx = ctx or default_context(dev)
-    arr, schema = geometry_column(col, large)
-    n = len(col)
+    arr, schema = geometry_column(col, large, offset, length)
+    n = arr.struct.array.length
     cells = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
-    valid = torch.empty((n + 7) // 8 + 1, dtype=torch.uint8, device=dev)
+    valid = _valid_buffer(out_valid, n, dev)
     s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
     N.check(N.lib().mgpu_geometry_to_cells_arrow(ctx.handle, isys.code, res, arr.ref, ctypes.byref(schema),
                                                  cells.data_ptr(), valid.data_ptr(), s))
-    return cells[:n], valid[:(n + 7) // 8]
+    return cells[:n], (valid if out_valid is not None else valid[:(n + 7) // 8])

@@ -45,8 +45,11 @@ class GeometryColumn:
 
     FORMATS = {"wkb": N.MGPU_GEOM_WKB, "wkt": N.MGPU_GEOM_WKT, "hex": N.MGPU_GEOM_HEX, "geojson": N.MGPU_GEOM_GEOJSON}
 
-    def __init__(self, fmt, data, offsets, valid=None):
+    def __init__(self, fmt, data, offsets, valid=None, valid_offset=0):
+        """``valid_offset``: the bit of row 0 in ``valid`` (a sliced column: ``offsets`` a
+        view of the parent's from that row on, the bitmap the parent's)."""
         self.format, self.data, self.offsets, self.valid = fmt, data, offsets, valid
+        self.valid_offset = int(valid_offset)
 
     def __len__(self):
         return self.offsets.numel() - 1
@@ -75,10 +78,13 @@ class InternalGeometryColumn:
     """Mosaic's InternalGeometryType column (InternalGeometry.scala: typeId, boundaries,
     holes) flattened as nested lists in device memory (mgpu_internal_geometry_to_cells):
     type_id[n]; row_part[n + 1]; part_ring[P + 1] (each part's boundary, then its holes);
-    ring_off[R + 1]; xy[2 V]."""
+    ring_off[R + 1]; xy[2 V].  ``valid``: optional validity bitmap (LSB first, 1 = present),
+    row 0's bit at ``valid_offset`` (a sliced column: type_id / row_part views of the
+    parent's from that row on)."""
 
-    def __init__(self, type_id, row_part, part_ring, ring_off, xy):
+    def __init__(self, type_id, row_part, part_ring, ring_off, xy, valid=None, valid_offset=0):
         self.type_id, self.row_part, self.part_ring, self.ring_off, self.xy = type_id, row_part, part_ring, ring_off, xy
+        self.valid, self.valid_offset = valid, int(valid_offset)
 
     def __len__(self):
         return self.type_id.numel()
@@ -102,58 +108,82 @@ class InternalGeometryColumn:
                                       T(np.array(xy, np.float64).reshape(-1, 2) if xy else np.zeros((1, 2)), np.float64))
 
 
-def grid_pointascellid(points, resolution, index_system=None, ctx=None, stream=None, stats=False):
+def _valid_buffer(out_valid, n, dev):
+    """The output bitmap of a geometry call: the caller's buffer (checked), or a fresh one."""
+    import torch
+    if out_valid is None:
+        return torch.empty((n + 7) // 8 + 1, dtype=torch.uint8, device=dev)
+    if out_valid.dtype != torch.uint8 or out_valid.device != dev or not out_valid.is_contiguous() \
+            or out_valid.numel() < (n + 7) // 8:
+        raise N.IllegalArgumentException(N.MGPU_E_INVALID_ARG, "out_valid must be a contiguous uint8 tensor of at "
+                                         "least (n + 7) // 8 bytes on the column's device")
+    return out_valid
+
+
+def grid_pointascellid(points, resolution, index_system=None, ctx=None, stream=None, stats=False, out_valid=None):
     """grid_pointascellid (PointIndexGeom.scala:33-47): the cell of each row's centroid.
 
     ``points``: a GeometryColumn (WKB / HEX rows of any type, WKT / GeoJSON POINT or
     MULTIPOINT rows, decoded on the GPU and reduced to JTS's centroid; null rows give
     cell 0 -- returned with the validity bitmap as (cells, valid)), an
-    InternalGeometryColumn, an (n, 2) float64 tensor, or an (x, y) pair (a point's
-    centroid is the point itself, MosaicGeometryJTS.scala:60-64).  Types a format does
-    not build raise MGPU_E_UNSUPPORTED, an empty geometry IllegalStateException (JTS getX
-    on an empty point)."""
-    if isinstance(points, InternalGeometryColumn):
+    InternalGeometryColumn (the same with a bitmap), an (n, 2) float64 tensor, or an (x, y)
+    pair (a point's centroid is the point itself, MosaicGeometryJTS.scala:60-64).  Types a
+    format does not build raise MGPU_E_UNSUPPORTED, an empty geometry IllegalStateException
+    (JTS getX on an empty point).  ``out_valid``: a caller-owned uint8 device buffer of at
+    least (n + 7) // 8 bytes for the returned bitmap (geometry columns; returned whole)."""
+    if isinstance(points, (InternalGeometryColumn, GeometryColumn)):
         import ctypes
         import torch
         from .context import default_context
         isys = index_system or _H3
         res = isys.get_resolution(resolution)
-        dev = points.type_id.device
+        internal = isinstance(points, InternalGeometryColumn)
+        dev = points.type_id.device if internal else points.offsets.device
         ctx = ctx or default_context(dev)
         n = len(points)
         cells = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+        valid = _valid_buffer(out_valid, n, dev) if (points.valid is not None or out_valid is not None) else None
+        in_valid = None if points.valid is None else points.valid.data_ptr()
+        out_ptr = None if valid is None else valid.data_ptr()
         st = N.MgpuStats()
         s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        N.check(N.lib().mgpu_internal_geometry_to_cells(ctx.handle, isys.code, res, n, points.type_id.data_ptr(),
-                                                        points.row_part.data_ptr(), points.part_ring.data_ptr(),
-                                                        points.ring_off.data_ptr(), points.xy.data_ptr(), None, 0,
-                                                        cells.data_ptr(), None, s, ctypes.byref(st)))
-        return (cells[:n], st.as_dict()) if stats else cells[:n]
-    if isinstance(points, GeometryColumn):
-        import ctypes
-        import torch
-        from .context import default_context
-        isys = index_system or _H3
-        res = isys.get_resolution(resolution)
-        dev = points.offsets.device
-        ctx = ctx or default_context(dev)
-        n = len(points)
-        cells = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
-        valid = torch.empty((n + 7) // 8 + 1, dtype=torch.uint8, device=dev) if points.valid is not None else None
-        st = N.MgpuStats()
-        s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        N.check(N.lib().mgpu_geometry_to_cells(ctx.handle, isys.code, res, points.format, points.data.data_ptr(),
-                                               points.offsets.data_ptr(),
-                                               None if points.valid is None else points.valid.data_ptr(), 0, n,
-                                               cells.data_ptr(), None if valid is None else valid.data_ptr(), s,
-                                               ctypes.byref(st)))
-        out = cells[:n] if valid is None else (cells[:n], valid[:(n + 7) // 8])
+        if internal:
+            N.check(N.lib().mgpu_internal_geometry_to_cells(ctx.handle, isys.code, res, n, points.type_id.data_ptr(),
+                                                            points.row_part.data_ptr(), points.part_ring.data_ptr(),
+                                                            points.ring_off.data_ptr(), points.xy.data_ptr(), in_valid,
+                                                            points.valid_offset, cells.data_ptr(), out_ptr, s,
+                                                            ctypes.byref(st)))
+        else:
+            N.check(N.lib().mgpu_geometry_to_cells(ctx.handle, isys.code, res, points.format, points.data.data_ptr(),
+                                                   points.offsets.data_ptr(), in_valid, points.valid_offset, n,
+                                                   cells.data_ptr(), out_ptr, s, ctypes.byref(st)))
+        if valid is None:
+            out = cells[:n]
+        else:
+            out = (cells[:n], valid if out_valid is not None else valid[:(n + 7) // 8])
         return (out, st.as_dict()) if stats else out
     if isinstance(points, (tuple, list)):
         x, y = points
     else:
         x, y = points[:, 0].contiguous(), points[:, 1].contiguous()
     return grid_longlatascellid(x, y, resolution, index_system=index_system, ctx=ctx, stream=stream, stats=stats)
+
+
+def points_from_geometry(col, ctx=None, stream=None):
+    """mgpu_points_from_geometry: the centroid of every row of a GeometryColumn as two
+    float64 device tensors (x, y); a null row gives NaN in both."""
+    import torch
+    from .context import default_context
+    dev = col.offsets.device
+    ctx = ctx or default_context(dev)
+    n = len(col)
+    x = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
+    y = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
+    s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    N.check(N.lib().mgpu_points_from_geometry(ctx.handle, col.format, col.data.data_ptr(), col.offsets.data_ptr(),
+                                              None if col.valid is None else col.valid.data_ptr(), col.valid_offset,
+                                              n, x.data_ptr(), y.data_ptr(), s))
+    return x[:n], y[:n]
 
 
 def grid_cellkring(cells, k, index_system, loop_only=False, ctx=None, stream=None):
