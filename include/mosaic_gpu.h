@@ -125,6 +125,10 @@ int32_t mgpu_ctx_destroy(mgpu_ctx* ctx);
  *   "count_groups"    0 (default): mgpu_pip_join_count's aggregation kernel runs on its
  *                     resident grid; 1..65536: on at most this many workgroups (a test hook:
  *                     a small value makes every workgroup take many chunks or tiles)
+ *   "kring_batch"     0 (default): mgpu_grid_kring's H3 pentagon fallback takes as many cells
+ *                     per launch as fit its 256 MB of scratch; 1..2^31-1: at most this many
+ *                     (and still at most what fits; a test hook: a small value makes the
+ *                     fallback run in many batches)
  *   "raster", "raster_bng", "raster_sub", "raster_milli"
  *                     the chip-table builder of mgpu_chips_upload on this context
  *                     (mgpu_build_opts below)

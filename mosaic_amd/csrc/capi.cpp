@@ -1879,6 +1879,9 @@ int32_t mgpu_ctx_set_option(mgpu_ctx* ctx, const char* key, int64_t v) {
   } else if (k == "count_groups") {
     if (v < 0 || v > mgpu::kCountGroupsMax) return bad();
     o.count_groups = v;
+  } else if (k == "kring_batch") {
+    if (v < 0 || v > 2147483647LL) return bad();
+    o.kring_batch = v;
   } else if (k == "spin_us") {
     if (v < 0 || v > 10000000) return bad();
     o.spin_us = v;
@@ -1905,6 +1908,7 @@ int32_t mgpu_ctx_get_option(const mgpu_ctx* ctx, const char* key, int64_t* v) {
       {"bin_min_mb", o.bin_min_mb}, {"bin_min_points", o.bin_min_points}, {"bin_xcd", o.bin_xcd},
       {"bin_keys", o.bin_keys},     {"spin_us", o.spin_us},   {"ring_batch", o.ring_batch},       {"raster", o.raster},     {"raster_bng", o.raster_bng},
       {"bng_split", o.bng_split},   {"count_lds_slots", o.count_lds_slots}, {"count_groups", o.count_groups},
+      {"kring_batch", o.kring_batch},
       {"raster_sub", o.raster_sub}, {"raster_milli", o.raster_milli}};
   for (const auto& kv : all)
     if (strcmp(kv.first, key) == 0) {
@@ -2065,6 +2069,7 @@ int32_t mgpu_grid_kring(mgpu_ctx* ctx, int32_t index_system, const int64_t* cell
   if (n_fb) {
     const int64_t words = mgpu::kring_fallback_words(k);
     batch = std::max<int64_t>(1, std::min<int64_t>(n_fb, ((int64_t)256 << 20) / 8 / words));
+    if (ctx->opt.kring_batch > 0) batch = std::min(batch, ctx->opt.kring_batch);  // (option kring_batch)
     HIP_TRY(hipMalloc(&scratch, (size_t)batch * words * 8));
     for (int64_t j0 = 0; j0 < n_fb; j0 += batch)
       HIP_TRY(mgpu::launch_kring_fallback(cells, fb_idx, j0, std::min(n_fb, j0 + batch), k, loop_only, mc, chunk,

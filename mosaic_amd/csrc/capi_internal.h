@@ -21,6 +21,7 @@ struct mgpu_options {
   int64_t ring_batch = (int64_t)1 << 26;   // ring joins: candidate pairs held in scratch at a time
   int64_t count_lds_slots = 4096;         // mgpu_pip_join_count: LDS histograms up to this many polygons (kernels.h kCountLdsSlotsMax)
   int64_t count_groups = 0;               // mgpu_pip_join_count: at most this many workgroups aggregate (0: the resident grid; a test hook)
+  int64_t kring_batch = 0;                // mgpu_grid_kring: at most this many pentagon-fallback cells per launch (0: what fits the scratch; a test hook)
   int64_t bng_split = 0;                  // BNG dense tables: the split pipeline, the grid entry as the code (A/B r6: C4 2.43 vs 2.17 ms fused -- off)
   // the chip-table builder of mgpu_chips_upload on this context (mgpu_build_opts)
   int64_t raster = 1, raster_bng = 0, raster_sub = 16, raster_milli = 250;
