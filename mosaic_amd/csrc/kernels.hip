@@ -477,7 +477,9 @@ constexpr int kGMixCap = kTile;
 // G = true: the split pipeline's mixed points -- tile = chunk * kChunkTiles + t covers
 // list positions [t * kTile, ...) of the chunk's mixed list; the phases are the same,
 // the result is each point's (first chip, match mask) in mixed_res (no pair records).
-template <int IS, bool SLOW, int G = 0>
+// LEAN (pip_mixed_kernel, G = 2): the same tile with less carried across its two register
+// peaks, the H3 projection of phase 1 and the edge-parallel walk.
+template <int IS, bool SLOW, int G = 0, bool LEAN = false>
 __device__ __forceinline__ void join_tile(const JoinArgs& a, const uint32_t tile) {
   __shared__ uint32_t s_ncand, s_nmix;
   __shared__ uint32_t s_wave_tot[kBlock / 64];
@@ -722,6 +724,39 @@ __device__ __forceinline__ void join_tile(const JoinArgs& a, const uint32_t tile
                                                         s_cand_pj, s_cand_xy, s_first, s_cnt, s_mask, kNoCellAns,
                                                         hit && (kv[k] & kKeyDeep) != 0u);
     }
+  } else if (LEAN) {
+    // a chunk's first mixed tile (pip_mixed_kernel): the lane's four coordinate loads go
+    // out together and the item loop is unrolled.  As a loop (the path below) the
+    // projection's constants and the arguments' predicates are hoisted in front of it and
+    // carried through every item -- some 20 VGPRs and 40 SGPRs parked in VGPR lanes on top
+    // of the projection's own peak.  A first tile seldom has a second item: the further
+    // copies are skipped by their wave-uniform test.
+    double bx[kItems], by[kItems];
+#pragma unroll
+    for (int k = 0; k < kItems; k++) {
+      const int li = k * kBlock + threadIdx.x;
+      bx[k] = by[k] = 0.0;
+      if (MGPU_VALID(li)) {
+        bx[k] = MGPU_LDPT(&a.x[MGPU_PT(li)]);
+        by[k] = MGPU_LDPT(&a.y[MGPU_PT(li)]);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < kItems; k++) {
+      const int li = k * kBlock + threadIdx.x;
+      Range r{0, 0, 0};
+      bool deep = false;
+      if (MGPU_VALID(li) && pt_valid(a.valid, a.valid_off, MGPU_PT(li))) {
+        bool ok, tie;
+        uint32_t gi;
+        r = chip_probe<IS, SLOW>(a, MGPU_PT(li), bx[k], by[k], &ok, &tie, &gi, &deep);
+        if (gi != kNoEntry) r = grid_range(t.grid[gi], t.cell_ans_row != nullptr);
+        any_bad |= !ok;
+        any_tie |= tie;
+      }
+      phase1_item<SLOW, kCap, kStash, point_stash<G>()>(t, li, r, bx[k], by[k], any_tie, &s_ncand, s_cand_pj, s_cand_xy, s_first, s_cnt,
+                                                        s_mask, kNoCellAns, deep);
+    }
   } else {
     // one item ahead: item k + 1's coordinates load while item k projects
     double nx = 0.0, ny = 0.0;
@@ -913,12 +948,22 @@ __device__ __forceinline__ void join_tile(const JoinArgs& a, const uint32_t tile
           if (f >= total) continue;
           const int bits = pip::count_segment(R[k].x, R[k].y, R[k].z, R[k].w, s_wx[wm[k]], s_wy[wm[k]]);
           if (!bits) continue;
-          const uint32_t rb = s_wone[wm[k]] ? 1u : 1u << t.edge_ring[we[k]];
+          // (LEAN: the record's index again from LDS, on this rare path only, not kept across the loads)
+          const uint32_t rb = s_wone[wm[k]] ? 1u : 1u << t.edge_ring[LEAN ? s_web[wm[k]] + (f - s_woff[wm[k]]) : we[k]];
           if (bits & pip::kRingOnSegment) atomicOr(&s_bnd[wm[k]], rb);
           if (bits & 2) atomicXor(&s_par[wm[k]], rb);
         }
       }
       __syncthreads();
+      if (LEAN) {
+        // (the walk's point and chip from LDS again: not carried across the edge loop)
+        asm volatile("" : "+v"(pj));
+        one = s_wone[lane] != 0;
+        px = s_wx[lane];
+        py = s_wy[lane];
+        li = pj & 1023;
+        ch = s_first[li] + (pj >> 10);
+      }
       if (lane < nmix && pip::strip_verdict(t, ch, one, fl, s_bnd[lane], s_par[lane], px, py))
         atomicOr(&s_mask[li], 1u << (pj >> 10));
       walked = true;
@@ -1564,9 +1609,14 @@ __global__ __launch_bounds__(kCfyBlock) __attribute__((amdgpu_waves_per_eu(MGPU_
 
 // The mixed points of one chunk per workgroup: its first tile of kTile; a chunk with
 // more queues its further tiles for pip_mixed_more_kernel (a loop over tiles here pinned
-// 23 more VGPRs: 5 waves/SIMD instead of 7).  (Measured and rejected, r3: the chunks'
-// lists packed into full tiles walked by a resident grid -- C2 mixed 0.22 -> 0.35 ms,
-// C5 0.60 -> 0.87: a full tile's phases take longer, and fewer tiles are in flight.)
+// 23 more VGPRs).  The H3 kernel takes 80 VGPRs, 6 waves/SIMD, with join_tile's LEAN
+// paths (87, 5 waves, without; its 6,152 B of LDS allow 26 one-wave workgroups per CU,
+// 6.5 per SIMD, so 72 VGPRs would buy half a wave more).  (Measured and rejected, r3: the
+// chunks' lists packed into full tiles walked by a resident grid -- C2 mixed 0.22 -> 0.35
+// ms, C5 0.60 -> 0.87: a full tile's phases take longer, and fewer tiles are in flight.)
+#ifndef MGPU_MIXED_LEAN
+#define MGPU_MIXED_LEAN 1
+#endif
 template <int IS>
 __global__ __launch_bounds__(kBlock) MGPU_JOIN_ATTR void pip_mixed_kernel(JoinArgs a) {
   const uint32_t nm = a.chunk_mixed[blockIdx.x];
@@ -1575,7 +1625,7 @@ __global__ __launch_bounds__(kBlock) MGPU_JOIN_ATTR void pip_mixed_kernel(JoinAr
     const uint32_t q = atomicAdd(a.n_extra, more);
     for (uint32_t t = 0; t < more; t++) a.extra[q + t] = blockIdx.x * kChunkTiles + 1 + t;
   }
-  join_tile<IS, false, 2>(a, blockIdx.x * kChunkTiles);
+  join_tile<IS, false, 2, MGPU_MIXED_LEAN != 0>(a, blockIdx.x * kChunkTiles);
 }
 
 template <int IS>
@@ -1650,23 +1700,48 @@ __device__ __forceinline__ uint32_t emit_swz(uint32_t q) { return MGPU_EMIT_SWZ 
 #ifndef MGPU_EMIT_NT_OTHER
 #define MGPU_EMIT_NT_OTHER 0
 #endif
+// waves per SIMD asked of the compiler.  split_emit_kernel<H3> takes 57 VGPRs (8 waves)
+// and 16,416 B of LDS plus its class table -- 9 workgroups, 36 waves, per CU: the
+// registers set its occupancy, 8.  (Round 3's "8: 64 VGPRs, spills" forced the attribute
+// on a source that carried its decoded codes, see emit_forget.)
 #ifndef MGPU_EMIT_WAVES
-#define MGPU_EMIT_WAVES 5  // (8: 64 VGPRs, spills; 5: none, A/B equal or better)
+#define MGPU_EMIT_WAVES 7
+#endif
+#ifndef MGPU_EMIT_WAVES_BNG
+#define MGPU_EMIT_WAVES_BNG 5  // (the BNG codes are 32 bits: twice the code words; 76 VGPRs)
+#endif
+#ifndef MGPU_BIN_EMIT_WAVES
+#define MGPU_BIN_EMIT_WAVES 5  // (bin_emit_kernel: 76 VGPRs, as before it had a macro of its own)
 #endif
 // lonlat one-match classes answer from an LDS copy of raster_cls_poly, and the chunk's
-// mixed results (with the polygon of each one-chip match) are staged in LDS by one
+// mixed results (a one-chip match as its polygon) are staged in LDS by one
 // cooperative load at the start: the per-item loops below then touch no global memory
 // for the common cases.  (A/B r4, profiles/r4_emit_ab.txt: the loops' per-item global
 // loads -- mixed_res, chip_poly -- serialised ~16 dependent L2 round trips per wave; with
 // staging skipped entirely the kernel took 0.19 ms instead of 0.34.  A resident-grid
 // variant prefetching the next chunk measured slower, 0.45 ms.)
-constexpr int kEmitCls = 2048;  // classes staged in LDS (8 KB)
+constexpr int kEmitCls = 2048;  // at most this many classes staged in LDS (dynamic: 4 B per one-match class)
 constexpr int kEmitMres = 512;  // mixed results of a chunk staged in LDS (the rest: global)
 #ifndef MGPU_EMIT_MR
 #define MGPU_EMIT_MR 1
 #endif
+// the classes split_emit_kernel answers from LDS: the table's one-match classes
+__host__ __device__ inline uint32_t emit_cls_staged(const ChipTableView& t) {
+  const uint32_t n = t.raster_ncls < t.raster_pc[0] ? t.raster_ncls : t.raster_pc[0];
+  return n < (uint32_t)kEmitCls ? n : (uint32_t)kEmitCls;
+}
+// The thread's code words, made opaque to the compiler before each pass over them: it
+// otherwise decodes the 16 codes (and their compares, the point indices, the class
+// lookups) once, ahead of the passes and of the window loop, and carries them all -- 96
+// VGPRs.  Decoded again in each pass (a shift and a compare per code) the kernel fits
+// MGPU_EMIT_WAVES waves.
+template <int N>
+__device__ __forceinline__ void emit_forget(uint32_t (&w)[N]) {
+#pragma unroll
+  for (int i = 0; i < N; i++) asm volatile("" : "+v"(w[i]));
+}
 template <int IS>
-__global__ __launch_bounds__(kClsBlock) __attribute__((amdgpu_waves_per_eu(MGPU_EMIT_WAVES))) void split_emit_kernel(SplitArgs sa) {
+__global__ __launch_bounds__(kClsBlock) __attribute__((amdgpu_waves_per_eu(IS == MGPU_H3 ? MGPU_EMIT_WAVES : MGPU_EMIT_WAVES_BNG))) void split_emit_kernel(SplitArgs sa) {
   using Code = typename CodeOf<IS>::T;
   constexpr int kWords = kClsItems * (int)sizeof(Code) / 4;  // 32-bit words of a thread's codes
   static_assert(kWords % 4 == 0 && kWords >= 4, "whole 16-byte code loads per thread (MGPU_CLS_BLOCK 256 or 512)");
@@ -1675,9 +1750,9 @@ __global__ __launch_bounds__(kClsBlock) __attribute__((amdgpu_waves_per_eu(MGPU_
   __shared__ uint32_t s_w[2][kClsBlock / 64];
   __shared__ uint32_t s_poly[kEmitWin];  // staging: polygon id
   __shared__ uint16_t s_pt[kEmitWin];    // staging: point of the chunk
-  __shared__ int32_t s_cp[IS == MGPU_H3 ? kEmitCls : 1];
-  __shared__ uint64_t s_mr[MGPU_EMIT_MR ? kEmitMres : 1];  // mixed results: first chip | mask << 32
-  __shared__ int32_t s_mp[MGPU_EMIT_MR ? kEmitMres : 1];   // ... the polygon of a one-chip match
+  // mixed results: first chip | mask << 32; a one-chip match as its polygon | 1 << 32
+  __shared__ uint64_t s_mr[MGPU_EMIT_MR ? kEmitMres : 1];
+  extern __shared__ int32_t s_cp[];  // [emit_cls_staged(chips)]: dynamic LDS, sized at launch
   // (an override rerun: the chunks before the first whose count changed keep their
   // output, but for the rerun ones)
   if (sa.redo_affected && blockIdx.x < *sa.redo_first && !sa.redo_affected[blockIdx.x]) return;
@@ -1708,7 +1783,7 @@ __global__ __launch_bounds__(kClsBlock) __attribute__((amdgpu_waves_per_eu(MGPU_
   // (the chunk scans below order these LDS stores before the reads)
   uint32_t ncp = 0;
   if (IS == MGPU_H3) {
-    ncp = min(min(t.raster_ncls, t.raster_pc[0]), (uint32_t)kEmitCls);
+    ncp = emit_cls_staged(t);
     for (uint32_t i = threadIdx.x; i < ncp; i += kClsBlock) s_cp[i] = t.raster_cls_poly[i];
   }
   constexpr uint32_t kMr = MGPU_EMIT_MR ? (uint32_t)kEmitMres : 0u;
@@ -1718,8 +1793,7 @@ __global__ __launch_bounds__(kClsBlock) __attribute__((amdgpu_waves_per_eu(MGPU_
     for (uint32_t i = threadIdx.x; i < nms; i += kClsBlock) {
       const uint64_t v = a.mixed_res[c0 + i];
       const uint32_t m = (uint32_t)(v >> 32);
-      s_mr[i] = v;
-      s_mp[i] = __popc(m) == 1 ? t.chip_poly[(uint32_t)v + __builtin_ctz(m)] : 0;
+      s_mr[i] = __popc(m) == 1 ? (uint64_t)(uint32_t)t.chip_poly[(uint32_t)v + __builtin_ctz(m)] | (1ull << 32) : v;
     }
   }
 #endif
@@ -1738,6 +1812,7 @@ __global__ __launch_bounds__(kClsBlock) __attribute__((amdgpu_waves_per_eu(MGPU_
   uint32_t all_mixed;
   const uint32_t rank0 = chunk_excl_scan(nmix, s_w[0], &all_mixed);
   uint32_t npair = 0, r = rank0;
+  emit_forget(cw);
 #pragma unroll
   for (int k = 0; k < kClsItems; k++) {
     const Code c = code(k);
@@ -1761,6 +1836,7 @@ __global__ __launch_bounds__(kClsBlock) __attribute__((amdgpu_waves_per_eu(MGPU_
     if (off0 < w0 + kEmitWin && off0 + npair > w0) {
       uint32_t q = off0;
       r = rank0;
+      emit_forget(cw);
 #pragma unroll
       for (int k = 0; k < kClsItems; k++) {
         const Code c = code(k);
@@ -1769,10 +1845,9 @@ __global__ __launch_bounds__(kClsBlock) __attribute__((amdgpu_waves_per_eu(MGPU_
         int32_t one = 0;
         if (c == kMixed) {
           const uint32_t rr = r++;
-          if (rr < kMr && __popc((uint32_t)(s_mr[rr] >> 32)) == 1)
-            has_one = true, one = s_mp[rr];
-          else
-            v = mres(rr);
+          v = mres(rr);
+          if (rr < kMr && __popc((uint32_t)(v >> 32)) == 1)  // (staged: the polygon itself)
+            has_one = true, one = (int32_t)(uint32_t)v, v = 0;
         } else if (IS == MGPU_H3 && c != 0 && (uint32_t)c < ncp)
           has_one = true, one = s_cp[(uint32_t)c];  // classes below raster_pc[0] match once
         else if (c != 0)
@@ -2745,7 +2820,7 @@ __device__ __forceinline__ void bin_answers(const BinArgs& b, int64_t p0, uint64
 
 // ordered output of one input chunk (as split_emit_kernel: the chunk's pairs are one
 // contiguous range, staged in LDS a window at a time, written by consecutive lanes)
-__global__ __launch_bounds__(kClsBlock) __attribute__((amdgpu_waves_per_eu(MGPU_EMIT_WAVES))) void bin_emit_kernel(BinArgs b) {
+__global__ __launch_bounds__(kClsBlock) __attribute__((amdgpu_waves_per_eu(MGPU_BIN_EMIT_WAVES))) void bin_emit_kernel(BinArgs b) {
   const SplitArgs& sa = b.s;
   const ChipTableView& t = sa.j.chips;
   __shared__ uint32_t s_w[kClsBlock / 64];
@@ -3070,7 +3145,8 @@ static void launch_emit(const SplitArgs& a, int64_t nc, hipStream_t s) {
   // (A/B r5, profiles/r5/ab_classify_pair_emit_wave.txt: one wave per chunk -- wave scans,
   // no workgroup barrier, the class table loaded once per workgroup -- took the C2 emit
   // 0.255 -> 0.467 ms: rejected)
-  hipLaunchKernelGGL(split_emit_kernel<IS>, dim3((unsigned)nc), dim3(kClsBlock), 0, s, a);
+  const size_t lds = IS == MGPU_H3 ? (size_t)emit_cls_staged(a.j.chips) * 4 : 0;  // (s_cp)
+  hipLaunchKernelGGL(split_emit_kernel<IS>, dim3((unsigned)nc), dim3(kClsBlock), lds, s, a);
 }
 
 template <int IS>
