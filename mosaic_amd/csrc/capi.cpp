@@ -1811,6 +1811,8 @@ int32_t mgpu_ctx_create(int32_t device_id, mgpu_ctx** out) {
       hipEventCreate(&c->ev2) != hipSuccess || hipEventCreate(&c->ev3) != hipSuccess ||
       hipHostMalloc((void**)&c->pin, kPinWords * 8, hipHostMallocDefault) != hipSuccess)
     st = fail(MGPU_E_DEVICE, "mgpu_ctx_create: events / pinned page");
+  if (!st && hipHostGetDevicePointer((void**)&c->pin_dev, c->pin, 0) != hipSuccess)
+    st = fail(MGPU_E_DEVICE, "mgpu_ctx_create: the pinned page is not device-visible");
   if (!st) st = ensure_ws(c, 1);
   if (!st) st = ensure_tq(c, kTqInit);
   if (st) {
@@ -3238,8 +3240,8 @@ static int32_t join_impl(mgpu_ctx* ctx, const mgpu_chips* chips, int32_t is, int
   a.extra = nullptr;
   a.n_extra = nullptr;
   a.poly_answers = 0;
-  HIP_TRY(hipMemsetAsync(base, 0, kWsCounters, s));
-  HIP_TRY(hipMemsetAsync(ctx->tq, 0, 16, s));
+  static_assert(kWsCounters == mgpu::kCounterWords * 8, "launch_join_clear clears the counters");
+  HIP_TRY(mgpu::launch_join_clear(a.counters, ctx->tq, s));  // (counters + the queue's header: one launch)
   // the split pipeline (kernels.h SplitArgs) when the chip table has a pixel index for
   // this resolution and no cell holds more than 32 chips
   // (BNG dense tables without a pixel index: the grid entry is the code -- a cell whose
@@ -3277,7 +3279,7 @@ static int32_t join_impl(mgpu_ctx* ctx, const mgpu_chips* chips, int32_t is, int
     a.extra = sa.extra = (uint32_t*)(sb + o_extra);
     a.n_extra = (uint32_t*)(a.counters + 7);  // (zeroed with the counters)
     a.group_sum = sa.chunk_pairs;
-    a.group_cand = (uint32_t*)(sb + o_cand);
+    a.group_cand = (uint32_t*)(sb + o_cand);  // (zeroed per chunk by the classify kernels)
     a.mixed_idx = sa.mixed_idx;
     a.mixed_res = (uint64_t*)(sb + o_res);
     a.chunk_mixed = sa.chunk_mixed;
@@ -3287,7 +3289,6 @@ static int32_t join_impl(mgpu_ctx* ctx, const mgpu_chips* chips, int32_t is, int
     sa.out_point = out_point;
     sa.out_poly = out_poly;
     sa.j = a;
-    HIP_TRY(hipMemsetAsync(a.group_cand, 0, nc * 4, s));
   }
   mgpu::BinArgs ba{};
   const bool binned = !split && plan_bins(o, chips, is, res, n, valid, a, ba);
@@ -3533,8 +3534,9 @@ static int32_t settle_join(mgpu_ctx* ctx, const JoinCall& c, bool timed, bool re
   int overflows = 0;
   uint64_t h[8] = {0};
   for (;;) {
-    HIP_TRY(hipMemcpyAsync(ctx->pin, ctx->ws, 16 * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(ctx->pin + 16, ctx->tq, (2 + 4 * kTqHead) * 8, hipMemcpyDeviceToHost, s));
+    // the counters and the queue's head, written into the pinned page by one launch
+    static_assert(kPinWords == mgpu::kCounterWords + 2 + 4 * kTqHead, "launch_join_readback fills the pinned page");
+    HIP_TRY(mgpu::launch_join_readback((const unsigned long long*)ctx->ws, ctx->tq, (int)(2 + 4 * kTqHead), ctx->pin_dev, s));
     HIP_TRY(stream_wait(ctx, s));
     memcpy(h, ctx->pin, sizeof h);
     const int64_t queued = (int64_t)ctx->pin[16];

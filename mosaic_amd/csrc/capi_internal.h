@@ -49,6 +49,7 @@ struct mgpu_ctx {
   uint64_t* ovr = nullptr;
   int64_t ovr_cap = 0;
   uint64_t* pin = nullptr;
+  uint64_t* pin_dev = nullptr;            // the page as kernels address it (launch_join_readback)
   // scratch of the geometry / Arrow entries (decoded points, validity bitmaps), grown on demand
   void* scratch = nullptr;
   size_t scratch_bytes = 0;

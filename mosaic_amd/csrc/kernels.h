@@ -181,6 +181,14 @@ hipError_t launch_cells(int is, int res, const double* x, const double* y, int64
                         unsigned long long* counters, unsigned long long* ties, int64_t tie_cap,
                         uint64_t* tie_queue, int64_t tq_cap, hipStream_t s, const uint8_t* valid = nullptr,
                         int64_t voff = 0);
+// A join's first and last stream operations (capi.cpp join_impl / settle_join), one launch
+// each: the 16 counter words and the near-tie queue's two header words cleared; and the
+// counters followed by the queue's first tq_words words written to `pin` (pinned host
+// memory, device-visible) for the host to read after the stream has drained.
+constexpr int kCounterWords = 16;  // a join's counters (u64)
+hipError_t launch_join_clear(unsigned long long* counters, uint64_t* tie_queue, hipStream_t s);
+hipError_t launch_join_readback(const unsigned long long* counters, const uint64_t* tie_queue, int tq_words,
+                                uint64_t* pin, hipStream_t s);
 // out[pos[k]] = val[k], k < n (the host's libm corrections of near-tie cells)
 hipError_t launch_scatter_i64(const int64_t* pos, const int64_t* val, int64_t n, int64_t* out, hipStream_t s);
 // x[pos[k]], y[pos[k]] -> xy[2k], xy[2k + 1] (coordinates of a few points, for the host)

@@ -1458,6 +1458,7 @@ __global__ __launch_bounds__(kCfyBlock) __attribute__((amdgpu_waves_per_eu(MGPU_
     if (lane == 0) {
       sa.chunk_pairs[ch] = pairs;
       sa.chunk_mixed[ch] = nmixed;
+      a.group_cand[ch] = 0;  // (the mixed tiles add to it, after this kernel on the stream)
     }
   }
   count_wave(&a.counters[2], any_bad);
@@ -1602,6 +1603,7 @@ __global__ __launch_bounds__(kCfyBlock) __attribute__((amdgpu_waves_per_eu(MGPU_
     if (lane == 0) {
       sa.chunk_pairs[ch] = pairs;
       sa.chunk_mixed[ch] = nmixed;
+      a.group_cand[ch] = 0;  // (the mixed tiles add to it, after this kernel on the stream)
     }
   }
   count_wave(&a.counters[2], any_bad);
@@ -1900,22 +1902,34 @@ __global__ __launch_bounds__(kScanBlock) void tile_scan_kernel(const uint32_t* _
   // thread i owns the contiguous run [i * per, (i + 1) * per): every load is issued
   // before the one workgroup scan of the run sums (a loop of block scans waits on each)
   __shared__ unsigned long long s_w[kScanBlock / 64];
-  __shared__ uint32_t s_v[kScanLds];          // the counts, loaded coalesced (ng <= kScanLds)
+  // the counts, loaded coalesced (ng <= kScanLds).  Count i = t * per + j of thread t's run
+  // lies at s_v[t * stride + j] with stride = per | 1: an odd stride puts the 32 runs a
+  // pass of LDS reads walks on 32 banks (runs of 24, unpadded, start on 4: 16-way conflicts)
+  __shared__ uint32_t s_v[kScanLds + kScanBlock];
   __shared__ unsigned long long s_base[kScanBlock];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t per = (ng + kScanBlock - 1) / kScanBlock;
   const int64_t b = threadIdx.x * per, e = b + per < ng ? b + per : ng;
   unsigned long long cand = 0, sum = 0;
   const bool lds = ng <= kScanLds;
+  // (LDS path, 32-bit: the coalesced passes' count i = threadIdx.x + 1024 k is j0-th of
+  // run q0; each step adds 1024 = dq * per + dr without a division)
+  const uint32_t per32 = lds && per > 0 ? (uint32_t)per : 1u, stride = per32 | 1u;
+  const uint32_t q0 = threadIdx.x / per32, j0 = threadIdx.x % per32;
+  const uint32_t dq = (uint32_t)kScanBlock / per32, dr = (uint32_t)kScanBlock % per32;
+  const uint32_t run0 = threadIdx.x * stride, nrun = (uint32_t)(e > b ? e - b : 0);
   if (lds) {
     // coalesced loads (every count in flight at once), then each thread's contiguous run
     // from LDS; offsets written back coalesced
-    for (int64_t i = threadIdx.x; i < ng; i += kScanBlock) {
+    uint32_t q = q0, j = j0;
+    for (uint32_t i = threadIdx.x; i < (uint32_t)ng; i += kScanBlock) {
       cand += gcand[i];
-      s_v[i] = gsum[i];
+      s_v[q * stride + j] = gsum[i];
+      q += dq, j += dr;
+      if (j >= per32) j -= per32, q++;
     }
     __syncthreads();
-    for (int64_t i = b; i < e; i++) sum += s_v[i];
+    for (uint32_t k = 0; k < nrun; k++) sum += s_v[run0 + k];
   } else {
     for (int64_t i = b; i < e; i++) {
       cand += gcand[i];
@@ -1941,13 +1955,18 @@ __global__ __launch_bounds__(kScanBlock) void tile_scan_kernel(const uint32_t* _
     // s_v[i] = the offset of i within its thread's run (< 2^32), s_base = the run's base
     s_base[threadIdx.x] = run;
     uint32_t rel = 0;
-    for (int64_t i = b; i < e; i++) {
-      const uint32_t v = s_v[i];
-      s_v[i] = rel;
+    for (uint32_t k = 0; k < nrun; k++) {
+      const uint32_t v = s_v[run0 + k];
+      s_v[run0 + k] = rel;
       rel += v;
     }
     __syncthreads();
-    for (int64_t i = threadIdx.x; i < ng; i += kScanBlock) goff[i] = s_base[i / per] + s_v[i];
+    uint32_t q = q0, j = j0;
+    for (uint32_t i = threadIdx.x; i < (uint32_t)ng; i += kScanBlock) {
+      goff[i] = s_base[q] + s_v[q * stride + j];
+      q += dq, j += dr;
+      if (j >= per32) j -= per32, q++;
+    }
   } else {
     for (int64_t i = b; i < e; i++) {
       goff[i] = run;
@@ -2986,6 +3005,35 @@ hipError_t launch_cells(int is, int res, const double* x, const double* y, int64
     hipLaunchKernelGGL(cells_kernel<MGPU_BNG>, dim3((unsigned)blocks), dim3(kStreamBlock), 0, s, x, y, n, res, out,
                        counters, ties, tie_cap, valid, voff);
   }
+  return hipGetLastError();
+}
+
+// A join's first stream operation: its counters and the near-tie queue's header, in one
+// launch (as two fills each was a blit kernel of ~3 us between dependent neighbours).
+__global__ __launch_bounds__(64) void join_clear_kernel(unsigned long long* __restrict__ counters,
+                                                        uint64_t* __restrict__ tie_queue) {
+  if (threadIdx.x < kCounterWords) counters[threadIdx.x] = 0;
+  else if (threadIdx.x < kCounterWords + 2) tie_queue[threadIdx.x - kCounterWords] = 0;
+}
+
+// ... and its last: the counters, then the queue's first tq_words words, into the host's
+// pinned page (one launch for two device-to-host copies)
+__global__ __launch_bounds__(256) void join_readback_kernel(const unsigned long long* __restrict__ counters,
+                                                            const uint64_t* __restrict__ tie_queue, int tq_words,
+                                                            uint64_t* __restrict__ pin) {
+  for (int i = threadIdx.x; i < kCounterWords + tq_words; i += 256)
+    pin[i] = i < kCounterWords ? (uint64_t)counters[i] : tie_queue[i - kCounterWords];
+  __threadfence_system();
+}
+
+hipError_t launch_join_clear(unsigned long long* counters, uint64_t* tie_queue, hipStream_t s) {
+  hipLaunchKernelGGL(join_clear_kernel, dim3(1), dim3(64), 0, s, counters, tie_queue);
+  return hipGetLastError();
+}
+
+hipError_t launch_join_readback(const unsigned long long* counters, const uint64_t* tie_queue, int tq_words,
+                                uint64_t* pin, hipStream_t s) {
+  hipLaunchKernelGGL(join_readback_kernel, dim3(1), dim3(256), 0, s, counters, tie_queue, tq_words, pin);
   return hipGetLastError();
 }
 
