@@ -408,6 +408,29 @@ int32_t mgpu_pip_join_count(mgpu_ctx* ctx, const mgpu_chips* chips, int32_t inde
                             const double* x, const double* y, const int64_t* weight, int64_t n, int64_t n_slots,
                             int64_t* count, int64_t* sum, int32_t accumulate, void* stream, mgpu_stats* stats);
 
+/* The join as a per-point column, in input order: "which zone is this trip in?" -- the
+ * Quickstart's join (notebooks/examples/python/Quickstart/QuickstartNotebook.ipynb:1835)
+ * taken as a left join of the points with the chips and first(polygon) per point, over the predicate
+ * of ST_Contains.scala:21-44.  For input position i:
+ *   out_polygon[i]  the polygon id of the first pair mgpu_pip_join emits for point i on the
+ *                   same inputs -- the lowest matching id -- or null_id when it has none;
+ *   out_matches[i]  the number of pairs mgpu_pip_join emits for point i (0: none; more than
+ *                   1: overlapping polygons).  May be NULL: then it is not written.  With it
+ *                   a host builds a validity bitmap whatever null_id is.
+ * Both are device int32[n]; every element of [0, n) is written exactly once by a successful
+ * call (no pre-fill needed), and only after the join has settled (near-tie queue, host libm
+ * pass, override rerun, as mgpu_pip_join): a failing call -- invalid coordinates raise the
+ * same errors as mgpu_pip_join -- leaves them untouched.  n == 0 is MGPU_OK and writes
+ * nothing; out_polygon == NULL with n > 0 is MGPU_E_INVALID_ARG.  No pairs are written and
+ * no output offsets computed: 4 or 8 bytes per point instead of 12 per pair.
+ * Synchronises `stream`; stats as mgpu_pip_join (n_pairs = the sum of the match counts;
+ * kernel_ms includes the lookup launch, emit_kernel_ms is its time).  The join's records
+ * stay in the context: mgpu_pip_join_fetch after this call writes the pairs mgpu_pip_join
+ * would have. */
+int32_t mgpu_pip_join_lookup(mgpu_ctx* ctx, const mgpu_chips* chips, int32_t index_system, int32_t res,
+                             const double* x, const double* y, int64_t n, int32_t null_id,
+                             int32_t* out_polygon, int32_t* out_matches, void* stream, mgpu_stats* stats);
+
 /* Asynchronous form, in two calls.  mgpu_pip_join_async enqueues the join on `stream`
  * and returns at once: the pair count is left in device memory (*d_n_pairs, one int64)
  * -- graph-capturable once mgpu_ctx_reserve has sized the workspace and one call of the

@@ -352,6 +352,20 @@ inline int64_t pipJoinCount(GpuContext& ctx, const DeviceChips& chips, const Ind
   return st.n_pairs;
 }
 
+// The join as a per-point column (mgpu_pip_join_lookup; device pointers): polygon_dev[i] =
+// the lowest polygon id matching point i, null_id without a match; matches_dev[i] = its
+// number of matches (null: not written).  One int32 per point each, every element written.
+// Returns the number of pairs (the sum of the match counts).
+inline int64_t pipJoinLookup(GpuContext& ctx, const DeviceChips& chips, const IndexSystem& is, int resolution,
+                             const double* x_dev, const double* y_dev, int64_t n, int32_t* polygon_dev,
+                             int32_t* matches_dev = nullptr, int32_t null_id = -1, void* stream = nullptr) {
+  const int r = is.getResolution(resolution);
+  mgpu_stats st{};
+  check(mgpu_pip_join_lookup(ctx.get(), chips.get(), is.code(), r, x_dev, y_dev, n, null_id, polygon_dev, matches_dev,
+                             stream, &st));
+  return st.n_pairs;
+}
+
 }  // namespace mosaic
 
 #endif  // MOSAIC_INDEX_SYSTEM_HPP

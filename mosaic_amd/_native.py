@@ -45,6 +45,7 @@ EXPORTS = (
     "mgpu_test_receive_blob", "mgpu_ring_join", "mgpu_ring_join_ex", "mgpu_ring_join_final",
     "mgpu_test_overlay_verify",
     "mgpu_chips_polygons", "mgpu_pip_join_count", "mgpu_test_poly_slots_host", "mgpu_chips_raster_info",
+    "mgpu_pip_join_lookup",
 )
 MGPU_GEOM_WKB = 0
 MGPU_GEOM_WKT = 1
@@ -191,6 +192,7 @@ def lib():
         "mgpu_test_receive_blob": (I32, [P, P, I32, ctypes.POINTER(P)]),
         "mgpu_chips_polygons": (I32, [P, P, I64, ctypes.POINTER(I64)]),
         "mgpu_pip_join_count": (I32, [P, P, I32, I32, P, P, P, I64, I64, P, P, I32, P, ctypes.POINTER(MgpuStats)]),
+        "mgpu_pip_join_lookup": (I32, [P, P, I32, I32, P, P, I64, I32, P, P, P, ctypes.POINTER(MgpuStats)]),
         "mgpu_test_poly_slots_host": (I32, [P, I64, P, ctypes.POINTER(I64), P]),
         "mgpu_ring_join": (I32, [P, I32, I32, I32, I32, P, P, I64, P, P, I64, I64, I32, ctypes.c_double, I64,
                                  ctypes.POINTER(I64), P, P, P, P]),

@@ -3803,6 +3803,54 @@ int32_t mgpu_pip_join_count(mgpu_ctx* ctx, const mgpu_chips* chips, int32_t is, 
   return MGPU_OK;
 }
 
+// As mgpu_pip_join_count: the join in count mode, settled as the pair join is, the fused
+// pipeline's one rerun with the pool it asked for -- then one lookup launch over what the
+// join left in device memory (kernels.h LookupArgs), which writes every element of the
+// outputs once.  Writing only after settle_join keeps a failing call's outputs untouched.
+int32_t mgpu_pip_join_lookup(mgpu_ctx* ctx, const mgpu_chips* chips, int32_t is, int32_t res, const double* x,
+                             const double* y, int64_t n, int32_t null_id, int32_t* out_polygon, int32_t* out_matches,
+                             void* stream, mgpu_stats* stats) {
+  if (!ctx || !chips) return fail(MGPU_E_INVALID_ARG, "ctx/chips is NULL");
+  if (n > 0 && !out_polygon) return fail(MGPU_E_INVALID_ARG, "pip_join_lookup: out_polygon is NULL");
+  const hipStream_t s = (hipStream_t)stream;
+  JoinCall c{chips, is, res, x, y, nullptr, 0, n, 0, nullptr, nullptr, s, nullptr, 0, nullptr, std::max<int64_t>(n, 0)};
+  const bool reference_libm = is == MGPU_H3 && ctx->opt.h3_libm == MGPU_LIBM_REFERENCE;
+  int64_t pairs = 0;
+  if (int32_t st = launch_call(ctx, c, true, 0, reference_libm)) return st;
+  if (int32_t st = settle_join(ctx, c, true, reference_libm, &pairs, stats)) return st;
+  auto& L = ctx->last;
+  if (!L.pool_ok) {
+    c.count_pool = L.pool_used;
+    if (int32_t st = launch_call(ctx, c, true, 0, reference_libm)) return st;
+    if (int32_t st = settle_join(ctx, c, true, reference_libm, &pairs, stats)) return st;
+    if (!L.pool_ok)
+      return fail(MGPU_E_INTERNAL, "pip_join_lookup: the overflow pool of %lld records is short again (%lld asked for)",
+                  (long long)L.pool, (long long)L.pool_used);
+  }
+  if (n == 0) return MGPU_OK;
+  mgpu::LookupArgs la{out_polygon, out_matches, null_id, (uint32_t*)((unsigned long long*)ctx->ws + kWsCountDropped)};
+  HIP_TRY(hipEventRecord(ctx->ev2, s));
+  if (L.split)
+    HIP_TRY(mgpu::launch_split_lookup(is, L.sargs, la, s));
+  else if (L.binned)
+    HIP_TRY(mgpu::launch_bin_lookup(L.bargs, la, s));
+  else
+    HIP_TRY(mgpu::launch_tile_lookup(L.emit, n, L.n_tiles, la, s));
+  HIP_TRY(hipEventRecord(ctx->ev3, s));
+  const bool fused = !L.split && !L.binned;  // (only tile_lookup_kernel sets the flag)
+  if (fused) HIP_TRY(hipMemcpyAsync(ctx->pin, la.dropped, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(stream_wait(ctx, s));
+  if (fused && ctx->pin[0])
+    return fail(MGPU_E_INTERNAL, "pip_join_lookup: a tile's records were dropped by the overflow pool");
+  if (stats) {
+    float ms = 0;
+    hipEventElapsedTime(&ms, ctx->ev2, ctx->ev3);
+    stats->emit_kernel_ms = ms;
+    stats->kernel_ms += ms;
+  }
+  return MGPU_OK;
+}
+
 int32_t mgpu_test_poly_slots_host(const int32_t* polygon_id, int64_t n, int32_t* out_ids, int64_t* out_n,
                                   uint32_t* out_slot_of_row) {
   if (n < 0 || !out_n || (n > 0 && (!polygon_id || !out_ids || !out_slot_of_row)))

@@ -246,6 +246,20 @@ constexpr int64_t kCountStageMax = 2048;     // lookup entries (dense table or s
 hipError_t launch_split_count(int is, const SplitArgs& a, const CountArgs& c, hipStream_t s);
 hipError_t launch_tile_count(const EmitArgs& e, int64_t n_tiles, const CountArgs& c, hipStream_t s);
 hipError_t launch_bin_count(const BinArgs& b, const CountArgs& c, hipStream_t s);
+
+// mgpu_pip_join_lookup's output (lookup_kernels.inc): per input position, the lowest
+// matching polygon id and the match count of the pairs a finished join left in device
+// memory.  One launch per pipeline, one unit (chunk / tiles) per workgroup, over what that
+// pipeline's count kernel reads; every element of [0, n) is written once.
+struct LookupArgs {
+  int32_t* out_polygon;   // [n] the point's first pair's polygon id, null_id without one
+  int32_t* out_matches;   // [n] its pairs, or null (not written)
+  int32_t null_id;
+  uint32_t* dropped;      // set when a fused tile's records were dropped by the overflow pool
+};
+hipError_t launch_split_lookup(int is, const SplitArgs& a, const LookupArgs& o, hipStream_t s);
+hipError_t launch_tile_lookup(const EmitArgs& e, int64_t n, int64_t n_tiles, const LookupArgs& o, hipStream_t s);
+hipError_t launch_bin_lookup(const BinArgs& b, const LookupArgs& o, hipStream_t s);
 // StringType cell ids: offsets[n + 1] (device); chunk: scratch of format_chunks(n) int64;
 // counters[2] += ids without a string form (BNG)
 int64_t format_chunks(int64_t n);

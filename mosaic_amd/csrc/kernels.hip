@@ -3365,5 +3365,6 @@ hipError_t launch_st_contains(const ChipTableView& t, const int64_t* row, const 
 }
 
 #include "count_kernels.inc"
+#include "lookup_kernels.inc"
 
 }  // namespace mgpu

@@ -375,6 +375,65 @@ def pip_join_count(x, y, chips, resolution, index_system=None, weight=None, out=
     return CountResult(chips.polygons_device(), cnt, sm, st.as_dict())
 
 
+class LookupResult:
+    """pip_join_lookup's result: ``polygon_id`` (int32 tensor, one per input point: its
+    lowest matching polygon id, ``null_id`` without a match), ``matches`` (int32 tensor,
+    the point's number of matches, or None when not asked for) and the stats dict."""
+
+    def __init__(self, polygon_id, matches, stats):
+        self.polygon_id = polygon_id
+        self.matches = matches
+        self.stats = stats
+
+    def __len__(self):
+        return self.polygon_id.numel()
+
+
+def pip_join_lookup(x, y, chips, resolution, index_system=None, null_id=-1, matches=True, out=None, stream=None):
+    """The join as a per-point column in input order (mgpu_pip_join_lookup): for point i,
+    the polygon id of the first pair pip_join emits for it on the same inputs -- the lowest
+    matching id -- or ``null_id`` when it has none, and (``matches``) the number of pairs
+    pip_join emits for it.  No pairs are written.
+
+    ``out`` = (polygon_id, matches) preallocated contiguous int32 device tensors of one
+    element per point (matches None exactly when ``matches`` is False); they are written in
+    place and returned.  Every element is written; a call that raises leaves them
+    untouched."""
+    import ctypes
+    import torch
+    isys = index_system or _H3
+    res = isys.get_resolution(resolution)
+    if isinstance(chips, ChipTable):
+        if chips.index_system != isys.code:
+            raise N.IllegalArgumentException(N.MGPU_E_INVALID_ARG, "chip table built for another index system")
+        chips = chips.upload()
+    _check_points(x, y)
+    n = x.numel()
+    if chips.ctx.device != x.device:
+        raise N.IllegalArgumentException(N.MGPU_E_INVALID_ARG, "chip table on %s, points on %s" % (chips.ctx.device, x.device))
+    null_id = int(null_id)
+    if not -2 ** 31 <= null_id < 2 ** 31:
+        raise N.IllegalArgumentException(N.MGPU_E_INVALID_ARG, "null_id must fit an int32")
+    if out is not None:
+        op, om = out
+        for t, what in ((op, "polygon_id"), (om, "matches")):
+            if t is not None and (t.dtype != torch.int32 or t.device != x.device or not t.is_contiguous()
+                                  or t.numel() != n):
+                raise N.IllegalArgumentException(
+                    N.MGPU_E_INVALID_ARG, "out %s must be a contiguous int32 tensor on the points' device, one element per point" % what)
+        if op is None or (om is None) != (not matches):
+            raise N.IllegalArgumentException(N.MGPU_E_INVALID_ARG, "out must be (polygon_id, matches), matches None exactly when matches=False")
+    else:
+        op = torch.empty(n, dtype=torch.int32, device=x.device)
+        om = torch.empty(n, dtype=torch.int32, device=x.device) if matches else None
+    s = stream if stream is not None else torch.cuda.current_stream(x.device).cuda_stream
+    st = N.MgpuStats()
+    N.check(N.lib().mgpu_pip_join_lookup(chips.ctx.handle, chips.handle, isys.code, res, x.data_ptr(), y.data_ptr(), n,
+                                         null_id, op.data_ptr(), None if om is None else om.data_ptr(), s,
+                                         ctypes.byref(st)))
+    return LookupResult(op, om, st.as_dict())
+
+
 class AsyncJoin:
     """A join enqueued by pip_join_async: ``finish()`` settles it (mgpu_pip_join_finish:
     the stream's wait, the H3 near-ties recomputed with the reference's libm, a rerun only
