@@ -125,6 +125,16 @@ int32_t mgpu_ctx_destroy(mgpu_ctx* ctx);
  *   "count_groups"    0 (default): mgpu_pip_join_count's aggregation kernel runs on its
  *                     resident grid; 1..65536: on at most this many workgroups (a test hook:
  *                     a small value makes every workgroup take many chunks or tiles)
+ *   "cellagg_groups"  0 (default): the mgpu_cell_agg_add_* accumulation runs on its resident
+ *                     grid; 1..65536: on at most this many workgroups (a test hook: one
+ *                     workgroup then carries its LDS table over many chunks)
+ *   "cellagg_lds"     1 (default): each workgroup of that accumulation keeps an LDS hash
+ *                     table in front of the global one; 0: every addition goes to the
+ *                     global table
+ *   "cellagg_bin_min" a column of at least this many cells (default 2^22; one without a validity
+ *                     bitmap) that holds more distinct cells than an LDS table is first dealt
+ *                     into 512 bins by hash (a counting sort in context scratch, 8 or 16 B per
+ *                     cell), so that each workgroup's table holds the cells it meets; 0: never
  *   "kring_batch"     0 (default): mgpu_grid_kring's H3 pentagon fallback takes as many cells
  *                     per launch as fit its 256 MB of scratch; 1..2^31-1: at most this many
  *                     (and still at most what fits; a test hook: a small value makes the
@@ -430,6 +440,67 @@ int32_t mgpu_pip_join_count(mgpu_ctx* ctx, const mgpu_chips* chips, int32_t inde
 int32_t mgpu_pip_join_lookup(mgpu_ctx* ctx, const mgpu_chips* chips, int32_t index_system, int32_t res,
                              const double* x, const double* y, int64_t n, int32_t null_id,
                              int32_t* out_polygon, int32_t* out_matches, void* stream, mgpu_stats* stats);
+
+/* CellAggregate: counts and sums per cell of a stream of points -- what a grid user does
+ * with a cell column before any polygon exists: with_postcodes.groupBy("index_id").count()
+ * (notebooks/examples/python/TransformBNG/transform_join_bng.ipynb:5321), count and sum per
+ * index_id in the gridded-EO notebooks (notebooks/examples/python/EOGriddedSTAC/03. Gridded
+ * EO Data.ipynb:3194-3233), over the cells of IndexSystem.pointToIndex
+ * (IndexSystem.scala:237).  A hash aggregation in LDS and device memory instead of a sort
+ * of the 8 B/point cell column.  The handle lives across batches (and contexts of its
+ * device); all arithmetic is integer, so the results are exact and do not depend on
+ * scheduling, batch boundaries or table growth.  Every call synchronises `stream`; n == 0 is
+ * MGPU_OK and adds nothing; a NULL ctx or handle is MGPU_E_INVALID_ARG before the device is
+ * touched.  All column pointers are device pointers; n_cells / out_n are host pointers.
+ *
+ * create: an aggregate for (index_system, res) -- checked as mgpu_check_resolution does,
+ *   before anything else -- with a sum column iff with_sum != 0.  Memory: one open-addressing
+ *   table of 16 B (24 B with a sum) per entry, kept at most half full; it never grows with
+ *   the number of points, only with the number of distinct cells D: the table holds at most
+ *   4 entries per distinct cell (96 B with a sum) above a floor of 1024 entries, and 6 per
+ *   cell for the duration of a growth step (old and new table).  initial_cells sizes it at
+ *   create (entries = the power of two >= 2 * initial_cells, at least the floor), so an
+ *   aggregate created for D cells takes D cells without growing.
+ * add_points: adds the cells mgpu_points_to_cells writes for the same inputs and context
+ *   options -- the fast path, the near-tie queue, the host glibc pass under h3_libm =
+ *   reference -- one count each and weight[i] to the sum.  Invalid coordinates raise the
+ *   same errors.  The aggregate is touched only after the cells have settled: a failing call
+ *   leaves counts and sums untouched.  The cell column goes to context scratch (8 B/point,
+ *   and as much again, twice with a weight, for a column that is binned: option
+ *   "cellagg_bin_min") and is never returned.  stats as mgpu_points_to_cells fills it; emit_kernel_ms is the
+ *   aggregation's time (kernel_ms includes it).
+ * add_cells: adds a cell column, e.g. mgpu_geometry_to_cells' output.  Any int64 is a key: 0,
+ *   -1, INT64_MIN and INT64_MAX included (the table's free-slot marker is -1; the aggregate of
+ *   the key -1 is kept in a side record, so no key is lost to it).  valid: optional Arrow
+ *   bitmap at bit offset valid_offset; null rows add nothing.
+ * weight (both): device int64[n], accepted only on a with_sum aggregate, and with_sum
+ *   requires it: otherwise MGPU_E_INVALID_ARG.  Sums wrap in two's complement.
+ * add_counted: adds (cell, count, sum) records, count[i] >= 0; a record of count 0 adds
+ *   nothing (and creates no cell).  sum is given exactly on a with_sum aggregate.  Reloads a
+ *   fetched result, merges another rank's or another aggregate's, and is the table's own
+ *   rehash on growth.
+ * size: *n_cells = the number of distinct cells with count > 0.
+ * fetch: those cells ascending as signed int64 with their counts and sums into device
+ *   int64[capacity] columns (compaction and a radix sort on the device); out_sum is NULL
+ *   exactly when the aggregate has no sum.  *out_n is always the exact number of cells, on
+ *   MGPU_OK and on MGPU_E_CAPACITY (capacity < *out_n: nothing is written).  Non-destructive
+ *   and repeatable; adding may continue afterwards.
+ * clear: empties the aggregate and keeps its memory.
+ * Context options: "cellagg_groups", "cellagg_lds", "cellagg_bin_min" (mgpu_ctx_set_option). */
+typedef struct mgpu_cell_agg mgpu_cell_agg;
+int32_t mgpu_cell_agg_create(mgpu_ctx* ctx, int32_t index_system, int32_t res, int32_t with_sum,
+                             int64_t initial_cells, mgpu_cell_agg** out);
+int32_t mgpu_cell_agg_add_points(mgpu_ctx* ctx, mgpu_cell_agg* agg, const double* x, const double* y,
+                                 const int64_t* weight, int64_t n, void* stream, mgpu_stats* stats);
+int32_t mgpu_cell_agg_add_cells(mgpu_ctx* ctx, mgpu_cell_agg* agg, const int64_t* cells, const uint8_t* valid,
+                                int64_t valid_offset, const int64_t* weight, int64_t n, void* stream);
+int32_t mgpu_cell_agg_add_counted(mgpu_ctx* ctx, mgpu_cell_agg* agg, const int64_t* cells, const int64_t* count,
+                                  const int64_t* sum, int64_t n, void* stream);
+int32_t mgpu_cell_agg_size(mgpu_ctx* ctx, const mgpu_cell_agg* agg, int64_t* n_cells, void* stream);
+int32_t mgpu_cell_agg_fetch(mgpu_ctx* ctx, const mgpu_cell_agg* agg, int64_t capacity, int64_t* out_cell,
+                            int64_t* out_count, int64_t* out_sum, int64_t* out_n, void* stream);
+int32_t mgpu_cell_agg_clear(mgpu_ctx* ctx, mgpu_cell_agg* agg, void* stream);
+int32_t mgpu_cell_agg_destroy(mgpu_cell_agg* agg);
 
 /* Asynchronous form, in two calls.  mgpu_pip_join_async enqueues the join on `stream`
  * and returns at once: the pair count is left in device memory (*d_n_pairs, one int64)

@@ -17,6 +17,8 @@
 //                          (notebooks/examples/python/Quickstart/QuickstartNotebook.ipynb:1835)
 //   pipJoinCount           that join aggregated per polygon (counts and integer sums), no pair
 //                          output (joined_df.count(), docs/source/usage/quickstart.ipynb:692)
+//   CellAggregate          groupBy("index_id").count() / .agg(count, sum) over pointToIndex's cells
+//                          (notebooks/examples/python/TransformBNG/transform_join_bng.ipynb:5321)
 //
 // Batch methods take device pointers (HBM) and a hipStream_t (as void*); the scalar
 // forms of the reference run as a batch of one through the host-pointer entry points.
@@ -365,6 +367,52 @@ inline int64_t pipJoinLookup(GpuContext& ctx, const DeviceChips& chips, const In
                              stream, &st));
   return st.n_pairs;
 }
+
+// Counts (and, withSum, int64 sums of a weight) per cell of a stream of batches
+// (mgpu_cell_agg_*; device pointers): df.groupBy("index_id").count() / .agg(count, sum)
+// over pointToIndex's cells.  weight_dev / sum_dev are given exactly on a withSum aggregate.
+class CellAggregate {
+ public:
+  CellAggregate(GpuContext& ctx, const IndexSystem& is, int resolution, bool with_sum = false, int64_t initial_cells = 0)
+      : ctx_(ctx) {
+    check(mgpu_cell_agg_create(ctx.get(), is.code(), is.getResolution(resolution), with_sum ? 1 : 0, initial_cells, &agg_));
+  }
+  ~CellAggregate() { mgpu_cell_agg_destroy(agg_); }
+  CellAggregate(const CellAggregate&) = delete;
+  CellAggregate& operator=(const CellAggregate&) = delete;
+
+  void addPoints(const double* x_dev, const double* y_dev, const int64_t* weight_dev, int64_t n, void* stream = nullptr,
+                 mgpu_stats* stats = nullptr) {
+    check(mgpu_cell_agg_add_points(ctx_.get(), agg_, x_dev, y_dev, weight_dev, n, stream, stats));
+  }
+  void addCells(const int64_t* cells_dev, const int64_t* weight_dev, int64_t n, const uint8_t* valid_dev = nullptr,
+                int64_t valid_offset = 0, void* stream = nullptr) {
+    check(mgpu_cell_agg_add_cells(ctx_.get(), agg_, cells_dev, valid_dev, valid_offset, weight_dev, n, stream));
+  }
+  void addCounted(const int64_t* cells_dev, const int64_t* count_dev, const int64_t* sum_dev, int64_t n,
+                  void* stream = nullptr) {
+    check(mgpu_cell_agg_add_counted(ctx_.get(), agg_, cells_dev, count_dev, sum_dev, n, stream));
+  }
+  int64_t size(void* stream = nullptr) const {
+    int64_t n = 0;
+    check(mgpu_cell_agg_size(ctx_.get(), agg_, &n, stream));
+    return n;
+  }
+  // the distinct cells ascending with their counts and sums into device columns of
+  // `capacity` elements; returns their number (CapacityError.required when it is larger)
+  int64_t fetch(int64_t capacity, int64_t* cell_dev, int64_t* count_dev, int64_t* sum_dev, void* stream = nullptr) const {
+    int64_t n = 0;
+    const int32_t st = mgpu_cell_agg_fetch(ctx_.get(), agg_, capacity, cell_dev, count_dev, sum_dev, &n, stream);
+    check(st, n);
+    return n;
+  }
+  void clear(void* stream = nullptr) { check(mgpu_cell_agg_clear(ctx_.get(), agg_, stream)); }
+  mgpu_cell_agg* get() const { return agg_; }
+
+ private:
+  GpuContext& ctx_;
+  mgpu_cell_agg* agg_ = nullptr;
+};
 
 }  // namespace mosaic
 

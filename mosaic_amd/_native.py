@@ -46,6 +46,8 @@ EXPORTS = (
     "mgpu_test_overlay_verify",
     "mgpu_chips_polygons", "mgpu_pip_join_count", "mgpu_test_poly_slots_host", "mgpu_chips_raster_info",
     "mgpu_pip_join_lookup",
+    "mgpu_cell_agg_create", "mgpu_cell_agg_add_points", "mgpu_cell_agg_add_cells", "mgpu_cell_agg_add_counted",
+    "mgpu_cell_agg_size", "mgpu_cell_agg_fetch", "mgpu_cell_agg_clear", "mgpu_cell_agg_destroy",
 )
 MGPU_GEOM_WKB = 0
 MGPU_GEOM_WKT = 1
@@ -194,6 +196,14 @@ def lib():
         "mgpu_pip_join_count": (I32, [P, P, I32, I32, P, P, P, I64, I64, P, P, I32, P, ctypes.POINTER(MgpuStats)]),
         "mgpu_pip_join_lookup": (I32, [P, P, I32, I32, P, P, I64, I32, P, P, P, ctypes.POINTER(MgpuStats)]),
         "mgpu_test_poly_slots_host": (I32, [P, I64, P, ctypes.POINTER(I64), P]),
+        "mgpu_cell_agg_create": (I32, [P, I32, I32, I32, I64, ctypes.POINTER(P)]),
+        "mgpu_cell_agg_add_points": (I32, [P, P, P, P, P, I64, P, ctypes.POINTER(MgpuStats)]),
+        "mgpu_cell_agg_add_cells": (I32, [P, P, P, P, I64, P, I64, P]),
+        "mgpu_cell_agg_add_counted": (I32, [P, P, P, P, P, I64, P]),
+        "mgpu_cell_agg_size": (I32, [P, P, ctypes.POINTER(I64), P]),
+        "mgpu_cell_agg_fetch": (I32, [P, P, I64, P, P, P, ctypes.POINTER(I64), P]),
+        "mgpu_cell_agg_clear": (I32, [P, P, P]),
+        "mgpu_cell_agg_destroy": (I32, [P]),
         "mgpu_ring_join": (I32, [P, I32, I32, I32, I32, P, P, I64, P, P, I64, I64, I32, ctypes.c_double, I64,
                                  ctypes.POINTER(I64), P, P, P, P]),
         "mgpu_ring_join_ex": (I32, [P, I32, I32, I32, I32, P, P, I64, P, P, I64, I64, I32, ctypes.c_double, I32,

@@ -1790,6 +1790,13 @@ int32_t set_device(int dev) {
 
 }  // namespace
 
+namespace mgpu {
+int32_t begin_call(mgpu_ctx* ctx) {
+  if (int32_t st = set_device(ctx->device)) return st;
+  return ensure_ws(ctx, 1);
+}
+}  // namespace mgpu
+
 extern "C" {
 
 const char* mgpu_last_error(void) { return g_err.c_str(); }
@@ -1881,6 +1888,15 @@ int32_t mgpu_ctx_set_option(mgpu_ctx* ctx, const char* key, int64_t v) {
   } else if (k == "count_groups") {
     if (v < 0 || v > mgpu::kCountGroupsMax) return bad();
     o.count_groups = v;
+  } else if (k == "cellagg_groups") {
+    if (v < 0 || v > mgpu::kCountGroupsMax) return bad();
+    o.cellagg_groups = v;
+  } else if (k == "cellagg_bin_min") {
+    if (v < 0) return bad();
+    o.cellagg_bin_min = v;
+  } else if (k == "cellagg_lds") {
+    if (v != 0 && v != 1) return bad();
+    o.cellagg_lds = v;
   } else if (k == "kring_batch") {
     if (v < 0 || v > 2147483647LL) return bad();
     o.kring_batch = v;
@@ -1910,7 +1926,7 @@ int32_t mgpu_ctx_get_option(const mgpu_ctx* ctx, const char* key, int64_t* v) {
       {"bin_min_mb", o.bin_min_mb}, {"bin_min_points", o.bin_min_points}, {"bin_xcd", o.bin_xcd},
       {"bin_keys", o.bin_keys},     {"spin_us", o.spin_us},   {"ring_batch", o.ring_batch},       {"raster", o.raster},     {"raster_bng", o.raster_bng},
       {"bng_split", o.bng_split},   {"count_lds_slots", o.count_lds_slots}, {"count_groups", o.count_groups},
-      {"kring_batch", o.kring_batch},
+      {"kring_batch", o.kring_batch}, {"cellagg_groups", o.cellagg_groups}, {"cellagg_lds", o.cellagg_lds}, {"cellagg_bin_min", o.cellagg_bin_min},
       {"raster_sub", o.raster_sub}, {"raster_milli", o.raster_milli}};
   for (const auto& kv : all)
     if (strcmp(kv.first, key) == 0) {
@@ -1933,7 +1949,7 @@ int32_t mgpu_ctx_reserve(mgpu_ctx* ctx, int64_t max_points) {
 // points it cannot decide), then -- H3 with the reference's libm -- the route's near-ties
 // recomputed on the host (h3_glibc.cpp) and the cells that moves written back.  A
 // near-tie queue that overflowed is grown and the call redone.
-static int32_t cells_impl(mgpu_ctx* ctx, int32_t is, int32_t res, const double* x, const double* y, int64_t n,
+int32_t cells_impl(mgpu_ctx* ctx, int32_t is, int32_t res, const double* x, const double* y, int64_t n,
                           int64_t* out_cell, hipStream_t s, const uint8_t* valid, int64_t voff, mgpu_stats* stats) {
   auto* counters = (unsigned long long*)ctx->ws;
   auto* ties = (unsigned long long*)((uint8_t*)ctx->ws + ws_layout(1, 0).ties);
@@ -4096,7 +4112,7 @@ int32_t mgpu_test_blob_contains_host(const void* host_blob, int64_t bytes, int64
 
 // ------------------------------------------------------------------ geometry columns, Arrow
 
-static int32_t ensure_scratch(mgpu_ctx* ctx, size_t bytes) {
+int32_t ensure_scratch(mgpu_ctx* ctx, size_t bytes) {
   if (bytes <= ctx->scratch_bytes) return MGPU_OK;
   if (ctx->scratch) HIP_TRY(hipFree(ctx->scratch));
   ctx->scratch = nullptr;

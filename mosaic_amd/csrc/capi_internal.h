@@ -22,6 +22,9 @@ struct mgpu_options {
   int64_t count_lds_slots = 4096;         // mgpu_pip_join_count: LDS histograms up to this many polygons (kernels.h kCountLdsSlotsMax)
   int64_t count_groups = 0;               // mgpu_pip_join_count: at most this many workgroups aggregate (0: the resident grid; a test hook)
   int64_t kring_batch = 0;                // mgpu_grid_kring: at most this many pentagon-fallback cells per launch (0: what fits the scratch; a test hook)
+  int64_t cellagg_groups = 0;             // mgpu_cell_agg_add_*: at most this many workgroups accumulate (0: the resident grid; a test hook)
+  int64_t cellagg_lds = 1;                // ... behind a per-workgroup LDS hash table (0: every addition goes to the global table)
+  int64_t cellagg_bin_min = (int64_t)1 << 22;  // ... columns of at least this many cells are binned by hash first when they hold many distinct cells (0: never)
   int64_t bng_split = 0;                  // BNG dense tables: the split pipeline, the grid entry as the code (A/B r6: C4 2.43 vs 2.17 ms fused -- off)
   // the chip-table builder of mgpu_chips_upload on this context (mgpu_build_opts)
   int64_t raster = 1, raster_bng = 0, raster_sub = 16, raster_milli = 250;
@@ -109,4 +112,13 @@ int64_t blob_bytes_of_header(const void* header);
 constexpr int64_t kBlobHeaderSize = 1024;
 // Take ownership of a device allocation holding a complete blob (no copy).
 int32_t adopt_device_blob(mgpu_ctx* ctx, void* dev_blob, int64_t bytes, mgpu_chips** out);
+// What a call that uses the workspace does first: the context's device made current, the
+// last join's records given up (capi.cpp ensure_ws).
+int32_t begin_call(mgpu_ctx* ctx);
 }  // namespace mgpu
+
+// capi.cpp, shared with cell_agg.hip: mgpu_points_to_cells' body (after begin_call; out_cell
+// a device column) and the context's scratch buffer, grown to at least `bytes`.
+int32_t cells_impl(mgpu_ctx* ctx, int32_t is, int32_t res, const double* x, const double* y, int64_t n,
+                   int64_t* out_cell, hipStream_t s, const uint8_t* valid, int64_t voff, mgpu_stats* stats);
+int32_t ensure_scratch(mgpu_ctx* ctx, size_t bytes);

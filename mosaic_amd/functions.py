@@ -434,6 +434,149 @@ def pip_join_lookup(x, y, chips, resolution, index_system=None, null_id=-1, matc
     return LookupResult(op, om, st.as_dict())
 
 
+class CellCounts:
+    """CellAggregate.result(): ``cell`` (int64 tensor, the distinct cells ascending),
+    ``count`` (int64 tensor, rows per cell) and ``sum`` (int64 tensor, the weights summed
+    per cell, or None on an aggregate without a sum)."""
+
+    def __init__(self, cell, count, sum):
+        self.cell = cell
+        self.count = count
+        self.sum = sum
+
+    def __len__(self):
+        return self.cell.numel()
+
+
+def _i64_column(t, what, n=None, device=None):
+    import torch
+    if t.dtype != torch.int64 or not t.is_cuda or (device is not None and t.device != device) or (
+            n is not None and t.numel() != n):
+        raise N.IllegalArgumentException(N.MGPU_E_INVALID_ARG,
+                                         "%s must be an int64 device tensor on the aggregate's device, one value per row" % what)
+    return t.contiguous()
+
+
+class CellAggregate:
+    """Counts (and, ``with_sum``, int64 sums of a weight) per cell of a stream of batches
+    (mgpu_cell_agg_*): ``df.groupBy("index_id").count()`` / ``.agg(count, sum)`` over
+    grid_longlatascellid's cells, without the cell column and without a sort.  Integer
+    arithmetic: the result is exact and does not depend on how the stream was cut into
+    batches.  ``initial_cells`` sizes the table for that many distinct cells; it grows on
+    demand."""
+
+    def __init__(self, index_system, resolution, with_sum=False, initial_cells=0, ctx=None):
+        import ctypes
+        from .context import default_context
+        self.index_system = index_system or _H3
+        self.resolution = self.index_system.get_resolution(resolution)
+        self.with_sum = bool(with_sum)
+        self.ctx = ctx or default_context()
+        self.handle = None
+        h = ctypes.c_void_p()
+        N.check(N.lib().mgpu_cell_agg_create(self.ctx.handle, self.index_system.code, self.resolution,
+                                             1 if self.with_sum else 0, int(initial_cells), ctypes.byref(h)))
+        self.handle = h
+
+    def _stream(self, stream):
+        import torch
+        return stream if stream is not None else torch.cuda.current_stream(self.ctx.device).cuda_stream
+
+    def add_points(self, x, y, weight=None, stream=None, stats=False):
+        """One count per point at its cell (grid_longlatascellid's), ``weight`` (int64, one
+        per point; exactly on a with_sum aggregate) to the cell's sum.  A call that raises
+        -- invalid coordinates, as grid_longlatascellid -- leaves the aggregate unchanged."""
+        import ctypes
+        _check_points(x, y)
+        n = x.numel()
+        if weight is not None:
+            weight = _i64_column(weight, "weight", n, x.device)  # (bound here: alive until the call returns)
+        st = N.MgpuStats()
+        N.check(N.lib().mgpu_cell_agg_add_points(self.ctx.handle, self.handle, x.data_ptr(), y.data_ptr(),
+                                                 None if weight is None else weight.data_ptr(), n,
+                                                 self._stream(stream), ctypes.byref(st)))
+        return st.as_dict() if stats else None
+
+    def add_cells(self, cells, weight=None, valid=None, valid_offset=0, stream=None):
+        """A cell column (any int64 values); ``valid``: optional Arrow validity bitmap (uint8
+        device tensor) read from bit ``valid_offset``: null rows add nothing."""
+        import torch
+        cells = _i64_column(cells, "cells")
+        n = cells.numel()
+        if weight is not None:
+            weight = _i64_column(weight, "weight", n, cells.device)
+        if valid is not None:
+            if valid.dtype != torch.uint8 or valid.device != cells.device or valid_offset < 0 or \
+                    valid.numel() * 8 < valid_offset + n:
+                raise N.IllegalArgumentException(N.MGPU_E_INVALID_ARG, "valid must be a uint8 device bitmap covering valid_offset + n bits")
+            valid = valid.contiguous()
+        N.check(N.lib().mgpu_cell_agg_add_cells(self.ctx.handle, self.handle, cells.data_ptr(),
+                                                None if valid is None else valid.data_ptr(), int(valid_offset),
+                                                None if weight is None else weight.data_ptr(), n, self._stream(stream)))
+
+    def add_counted(self, cells, count, sum=None, stream=None):
+        """(cell, count, sum) records -- a fetched result reloaded, another rank's or another
+        aggregate's result merged.  count >= 0; a record of count 0 adds nothing."""
+        cells = _i64_column(cells, "cells")
+        n = cells.numel()
+        count = _i64_column(count, "count", n, cells.device)
+        if sum is not None:
+            sum = _i64_column(sum, "sum", n, cells.device)
+        N.check(N.lib().mgpu_cell_agg_add_counted(self.ctx.handle, self.handle, cells.data_ptr(), count.data_ptr(),
+                                                  None if sum is None else sum.data_ptr(), n, self._stream(stream)))
+
+    def __len__(self):
+        import ctypes
+        n = ctypes.c_int64()
+        N.check(N.lib().mgpu_cell_agg_size(self.ctx.handle, self.handle, ctypes.byref(n), self._stream(None)))
+        return int(n.value)
+
+    def result(self, stream=None):
+        """The distinct cells ascending with their counts and sums (device tensors).  The
+        aggregate is unchanged: adding may continue."""
+        import ctypes
+        import torch
+        n = len(self)
+        dev = self.ctx.device
+        cell = torch.empty(n, dtype=torch.int64, device=dev)
+        cnt = torch.empty(n, dtype=torch.int64, device=dev)
+        sm = torch.empty(n, dtype=torch.int64, device=dev) if self.with_sum else None
+        got = ctypes.c_int64()
+        st = N.lib().mgpu_cell_agg_fetch(self.ctx.handle, self.handle, n, cell.data_ptr(), cnt.data_ptr(),
+                                         None if sm is None else sm.data_ptr(), ctypes.byref(got), self._stream(stream))
+        N.check(st, required=got.value)
+        return CellCounts(cell, cnt, sm)
+
+    def clear(self, stream=None):
+        """Empty the aggregate; its memory is kept."""
+        N.check(N.lib().mgpu_cell_agg_clear(self.ctx.handle, self.handle, self._stream(stream)))
+
+    def close(self):
+        if self.handle:
+            N.lib().mgpu_cell_agg_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def grid_cellcount(lon, lat, resolution, index_system=None, weight=None, ctx=None, stream=None):
+    """``groupBy(grid_longlatascellid(lon, lat, res)).count()`` (with ``weight``: and
+    ``sum(weight)``) in one call: CellCounts of the distinct cells ascending."""
+    from .context import default_context
+    # (sized for up to 2^20 distinct cells at once: 32 MiB; more cells grow the table)
+    agg = CellAggregate(index_system, resolution, with_sum=weight is not None,
+                        initial_cells=min(lon.numel(), 1 << 20), ctx=ctx or default_context(lon.device))
+    try:
+        agg.add_points(lon, lat, weight=weight, stream=stream)
+        return agg.result(stream=stream)
+    finally:
+        agg.close()
+
+
 class AsyncJoin:
     """A join enqueued by pip_join_async: ``finish()`` settles it (mgpu_pip_join_finish:
     the stream's wait, the H3 near-ties recomputed with the reference's libm, a rerun only
