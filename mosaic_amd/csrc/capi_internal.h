@@ -1,4 +1,5 @@
-// Internal: the C-ABI handle types and the helpers capi.cpp shares with comm.cpp.
+// Internal: the C-ABI handle types and the helpers capi.cpp and chip_build.cpp share with
+// comm.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -107,7 +108,8 @@ struct mgpu_chips {
 
 namespace mgpu {
 int32_t set_error(int32_t code, const char* fmt, ...);
-// Size of the whole chip-table blob from its 1 KiB header (host copy); 0 if not a blob.
+// Size of the whole chip-table blob from its 1 KiB header (host copy); 0 if not a blob
+// (chip_build.cpp).
 int64_t blob_bytes_of_header(const void* header);
 constexpr int64_t kBlobHeaderSize = 1024;
 // Take ownership of a device allocation holding a complete blob (no copy).

@@ -28,7 +28,7 @@
 // kernel's projection yields, not by the 64-bit cell id: the kernel then never
 // assembles H3 digits.  Every lattice position of every chip cell on every face a
 // point of that cell can project to is present (built and verified at upload with
-// face_ijk_to_h3, mosaic_amd/csrc/capi.cpp build_lattice).
+// face_ijk_to_h3, mosaic_amd/csrc/chip_build.cpp build_lattice).
 #pragma once
 #include <stdint.h>
 
@@ -151,7 +151,7 @@ struct ChipTableView {
   DenseFace dense[20];
   uint32_t bng_edge;
   double bng_inv_edge;
-  // Pixel index (kRaster*, capi.cpp build_raster): a raster of the chip cells' box in the
+  // Pixel index (kRaster*, chip_build.cpp build_raster): a raster of the chip cells' box in the
   // point coordinates whose pixel p holds a class: kPixEmpty (no point of the pixel has a
   // match), kPixMixed (the streaming kernel projects and tests the point), or k >= 1 =
   // raster_cls[k] = first chip | match mask << 32 -- every point of the pixel lies in
@@ -186,12 +186,12 @@ struct ChipTableView {
   // streaming kernel loads together with the pixel's class).
   uint32_t raster_sub_n, raster_sub_w;
   const RankWord* raster_rank;  // [ceil(ny * nx / 32)], or null: no second level / bands
-  // lonlat, instead of raster_rank (capi.cpp raster_bands): a refined mixed pixel's class
+  // lonlat, instead of raster_rank (chip_build.cpp raster_bands): a refined mixed pixel's class
   // is 0x8000 | its index within its band of 2^raster_band_shift rows, b = raster_band[iy
   // >> raster_band_shift] + (class & 0x7FFF); every other class is below 0x7FFF
   uint32_t raster_band_shift, raster_nband;
   const uint32_t* raster_band;  // [raster_nband], or null
-  // BNG dense grid: per-cell answer grids (capi.cpp build_cell_answers).  A cell with
+  // BNG dense grid: per-cell answer grids (chip_build.cpp build_cell_answers).  A cell with
   // border chips (at most kCellAnsChips) is cut into cell_ans_g x cell_ans_g squares of
   // cell_ans_sw whole metres; its grid entry carries kCellAnsFlag (bit 47: such tables
   // have no cell of 2^15 chips) and its index k among the dense row's answer cells (bits
@@ -204,7 +204,7 @@ struct ChipTableView {
   const uint32_t* cell_ans_row;  // [dense rows], or null: no answer grids
   const uint16_t* cell_ans;
   const uint16_t* raster_sub;
-  // lonlat with bands, palette-compressed (capi.cpp raster_palette; null: raster_sub holds
+  // lonlat with bands, palette-compressed (chip_build.cpp raster_palette; null: raster_sub holds
   // every block): block b's sub-pixel i has class (raster_pal[b] >> 16 k) & 0x7FFF (0x7FFF
   // = kPixMixed), k = the 2 bits (i & 3) of byte raster_idx2[b * sub_n^2 / 4 + i / 4];
   // raster_pal[b] with kPalFull: its classes are raster_sub[(raster_pal[b] & 0xFFFFFFFF) *
@@ -224,7 +224,7 @@ constexpr uint32_t kCellAnsChips = 15;      // chips of a cell with an answer gr
 constexpr uint16_t kCellAnsMixed = 0xFFFF;
 constexpr uint32_t kNoCellAns = 0xFFFFFFFFu;
 constexpr uint64_t kCellAnsFlag = 1ull << 47;
-// H3: core-mask bit 15 of a one-chip cell whose chip is the cell's own hexagon (capi.cpp
+// H3: core-mask bit 15 of a one-chip cell whose chip is the cell's own hexagon (chip_build.cpp
 // mark_whole_cells): a point deep inside the cell (FastHex::deep) matches it
 constexpr uint32_t kCoreWhole = 0x8000u;
 // the chip count of a dense grid entry (first | count << 32 | core mask << 48); `ans`: the

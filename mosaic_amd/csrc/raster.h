@@ -1,4 +1,4 @@
-// Pixel index lookup (chip_table.h "Pixel index"; built by capi.cpp build_raster_*),
+// Pixel index lookup (chip_table.h "Pixel index"; built by chip_build.cpp build_raster_*),
 // shared by the streaming join kernel and the host-side certificate test
 // (mgpu_test_raster_host).
 #pragma once

@@ -1,7 +1,7 @@
 """The chip table's pixel index, checked against the oracle on the CPU (no GPU needed).
 
 The streaming join kernel answers a point whose pixel is "pure" straight from the pixel
-(mosaic_amd/csrc/chip_table.h "Pixel index", built by capi.cpp build_raster_*): one
+(mosaic_amd/csrc/chip_table.h "Pixel index", built by chip_build.cpp build_raster_*): one
 certificate per pixel says that every point in it takes the same chip cell(s) and lies
 in the interior / exterior of each of their chips.  `mgpu_test_raster_host` builds the
 same table on the host and looks points up exactly as the kernel does
@@ -207,18 +207,30 @@ def test_whole_cell_shortcut_tracts_r10():
     print("whole-cell answers: %.3f of the points" % frac)
 
 
-def _blob_hash(c):
+def _blob_hash_of(index_system, cell, polygon_id, is_core, wkb_offsets, wkb, **opts):
     import ctypes
     import hashlib
     from mosaic_amd import _native as N
     out, nb = ctypes.c_void_p(), ctypes.c_int64()
     p = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
-    N.check(N.lib().mgpu_chips_host_blob(0, len(c), p(c.cell), p(c.polygon_id), p(c.is_core), p(c.wkb_offsets),
-                                         p(c.wkb), ctypes.byref(out), ctypes.byref(nb)))
+    arrays = (index_system, len(cell), p(cell), p(polygon_id), p(is_core), p(wkb_offsets), p(wkb))
+    if opts:  # (non-default build options: the _ex entry)
+        bo = N.BuildOpts()
+        N.lib().mgpu_build_opts_default(ctypes.byref(bo))
+        for k, v in opts.items():
+            assert hasattr(bo, k)
+            setattr(bo, k, v)
+        N.check(N.lib().mgpu_chips_host_blob_ex(*arrays, ctypes.byref(bo), ctypes.byref(out), ctypes.byref(nb)))
+    else:
+        N.check(N.lib().mgpu_chips_host_blob(*arrays, ctypes.byref(out), ctypes.byref(nb)))
     try:
         return nb.value, hashlib.sha256(ctypes.string_at(out.value, nb.value)).hexdigest()[:16]
     finally:
         N.lib().mgpu_host_free(out)
+
+
+def _blob_hash(c, **opts):
+    return _blob_hash_of(c.index_system, c.cell, c.polygon_id, c.is_core, c.wkb_offsets, c.wkb, **opts)
 
 
 def test_nyc_r9_blob_bytes_pinned(nyc_zones, nyc_chips_r9):
@@ -239,3 +251,48 @@ def test_nyc_r9_blob_bytes_pinned(nyc_zones, nyc_chips_r9):
     sh = M.tessellate(nyc_zones, M.H3IndexSystem(), 9, chip_geometry="sutherland_hodgman")
     assert _blob_hash(sh) == (86778624, 'd985992852f4d714')
     assert _blob_hash(nyc_chips_r9) == (86478848, '7e17fca5c22213e6')
+
+
+# The pins below were taken from the builder as it stood in capi.cpp, before it moved to
+# chip_build.cpp and build_blob was cut into phases (the parent commit's library, through
+# _blob_hash): the move and the split must not change a byte of any of them.
+
+
+def test_bng_london_r4_blob_bytes_pinned():
+    """BNG res 4: the dense (column, row) grid (its border cells are too few for the cell
+    answer grids: test_bng_london_r3_blob_bytes_pinned has those); with raster_bng=1 the BNG
+    pixel index too.  Values from the parent commit's builder."""
+    import bench_workloads as W
+    c = M.tessellate(W.london_districts(), M.BNGIndexSystem(), 4)
+    assert c.index_system == 1
+    assert _blob_hash(c) == (116649216, '133c0c92d535bbbd')
+    assert _blob_hash(c, raster_bng=1) == (135217408, '9bfaf1565747c85f')
+
+
+def test_bng_london_r3_blob_bytes_pinned():
+    """BNG res 3: the table with its cell answer grids (test_cell_answers_bng_london: res 4
+    leaves them out).  Values from the parent commit's builder."""
+    import bench_workloads as W
+    c = M.tessellate(W.london_districts(), M.BNGIndexSystem(), 3)
+    assert _blob_hash(c) == (36029184, '040be3e68030ad4a')
+
+
+def test_nyc_r4_hash_path_blob_bytes_pinned(nyc_zones):
+    """H3 res 4: build_lattice refuses res < 5, so the table probes by cell id through the
+    hash -- no dense grid, no pixel index.  Values from the parent commit's builder."""
+    c = M.tessellate(nyc_zones, M.H3IndexSystem(), 4)
+    assert _blob_hash(c) == (6094848, '959774f0996da68c')
+
+
+def test_nyc_r9_blob_bytes_pinned_with_options(nyc_chips_r9):
+    """NYC r9 built without the pixel index (raster=0) and without its sub-pixel level
+    (raster_sub=0).  Values from the parent commit's builder."""
+    assert _blob_hash(nyc_chips_r9, raster=0) == (15898368, '4fb2e649108f7edd')
+    assert _blob_hash(nyc_chips_r9, raster_sub=0) == (18363904, '21d07c428045f87a')
+
+
+def test_empty_table_blob_bytes_pinned():
+    """n_chips = 0, H3 and BNG.  Values from the parent commit's builder."""
+    e = lambda t, n=0: np.zeros(n, t)  # noqa: E731
+    for isys, pin in ((0, (8448, '4df153a7af2cd616')), (1, (8448, 'dbdddd82f6023ec5'))):
+        assert _blob_hash_of(isys, e(np.int64), e(np.int32), e(np.uint8), e(np.int64, 1), e(np.uint8)) == pin

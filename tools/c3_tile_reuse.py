@@ -93,7 +93,7 @@ def main():
     cs, core = cell[order], T["is_core"][order].astype(bool)
     wkb, off, memo = T["wkb"], T["wkb_offsets"], {}
 
-    def chip_bytes(j):  # (strips duplicate an edge into each strip it spans: ~1.5x, capi.cpp build_strips)
+    def chip_bytes(j):  # (strips duplicate an edge into each strip it spans: ~1.5x, chip_build.cpp build_strips)
         if j not in memo:
             r = order[j]
             memo[j] = HDR_BYTES + int(1.5 * EDGE_BYTES * edge_count(bytes(wkb[off[r]:off[r + 1]])))
