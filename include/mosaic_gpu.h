@@ -243,6 +243,55 @@ int32_t mgpu_grid_kring(mgpu_ctx* ctx, int32_t index_system, const int64_t* cell
                         int32_t loop_only, int64_t* out_cells, int64_t capacity, int64_t* out_offsets,
                         int64_t* out_total, void* stream);
 
+/* Cell id -> geometry over a device column of cells: what grid_boundaryaswkb /
+ * grid_boundary (expressions/index/IndexGeometry.scala:65-75) and grid_cellarea
+ * (expressions/index/CellArea.scala) compute per row.  Device pointers throughout; `valid`
+ * an optional Arrow validity bitmap read from bit valid_offset (as mgpu_geometry_to_cells),
+ * out_valid (optional) its copy at bit offset 0.  A null row gets 0 vertices, an empty WKB
+ * row, NaN centre and area.  A non-null row that is not a cell id fails the whole call with
+ * MGPU_E_INVALID_ARG before anything is written (the reference throws there or returns
+ * garbage) -- H3: mode != 1, base cell >= 122, a digit 7 at or before the resolution or
+ * another digit after it, a pentagon's deleted subsequence; BNG: the ids whose digits
+ * BNGIndexSystem.getResolution / getX / getY cannot decode.  Every entry reads that verdict
+ * back first (one small kernel and a wait on `stream`).
+ * H3 coordinates are H3 v3.7's h3ToGeoBoundary / h3ToGeo with correctly rounded sin, cos,
+ * asin, atan, atan2 (the reference's come from glibc's, which are not: DESIGN 3.8 has the
+ * measured gap, below 1e-12 degrees); mgpu_test_cell_geometry_host is the same code on
+ * the host, equal bit for bit.  BNG is integer arithmetic and exact.
+ *
+ * mgpu_cells_to_centers: IndexSystem.indexToCenter (IndexSystem.scala:239-241;
+ * H3IndexSystem.scala:230-233: h3ToGeo), out_x = lng, out_y = lat, degrees.  H3 only:
+ * MGPU_E_UNSUPPORTED for BNG (BNGIndexSystem.scala:518-520 throws NotImplementedError).
+ * The centres are queued on `stream`; the call does not wait for them. */
+int32_t mgpu_cells_to_centers(mgpu_ctx* ctx, int32_t index_system, const int64_t* cells, const uint8_t* valid,
+                              int64_t valid_offset, int64_t n, double* out_x, double* out_y, uint8_t* out_valid,
+                              void* stream);
+/* IndexSystem.indexToBoundary (IndexSystem.scala:243-245; H3IndexSystem.scala:235-237:
+ * h3ToGeoBoundary, not closed, 5 to 10 vertices with the distortion vertices of Class III
+ * cells on icosahedron edges) and the corners of BNGIndexSystem.indexToGeometry
+ * (BNGIndexSystem.scala:418-431: (x, y), (x + e, y), (x + e, y + e), (x, y + e)).  Row i:
+ * out_nverts[i] (x, y) pairs at out_xy[20 i ..] (16-byte aligned; the pairs beyond are
+ * left as they were).  The boundaries are queued on `stream`; the call does not wait for them. */
+int32_t mgpu_cells_to_boundaries(mgpu_ctx* ctx, int32_t index_system, const int64_t* cells, const uint8_t* valid,
+                                 int64_t valid_offset, int64_t n, double* out_xy, int32_t* out_nverts,
+                                 uint8_t* out_valid, void* stream);
+/* IndexSystem.indexToGeometry as WKB (H3IndexSystem.scala:103-112, BNGIndexSystem.scala:
+ * 418-431; IndexGeometry.scala:65-75): row i at out[out_offsets[i] .. out_offsets[i + 1]),
+ * big-endian 2-D, the bytes the tessellator's chips carry for a whole cell: a Polygon of one
+ * ring, the boundary closed with its first vertex; an H3 cell holding a pole as
+ * makePoleGeometry's cap (:361-384), one across the antimeridian cut in two (:386-410) --
+ * those few rows are shaped on the host from the device's boundaries.  out_offsets[n + 1]
+ * device int64.  Synchronises `stream`; *out_total = the bytes needed, MGPU_E_CAPACITY when
+ * out_bytes is below that (the rows that fit are written). */
+int32_t mgpu_cells_boundary_wkb(mgpu_ctx* ctx, int32_t index_system, const int64_t* cells, const uint8_t* valid,
+                                int64_t valid_offset, int64_t n, uint8_t* out, int64_t out_bytes, int64_t* out_offsets,
+                                int64_t* out_total, uint8_t* out_valid, void* stream);
+/* IndexSystem.area in km^2 (IndexSystem.scala:248-289: haversine sides and the spherical
+ * excess of the centre-vertex triangles, r = 6371.0088, operation for operation on the
+ * coordinates above; BNGIndexSystem.scala:510-516: (edge / 1000)^2).  Queued on `stream`. */
+int32_t mgpu_cells_area(mgpu_ctx* ctx, int32_t index_system, const int64_t* cells, const uint8_t* valid,
+                        int64_t valid_offset, int64_t n, double* out_area_km2, uint8_t* out_valid, void* stream);
+
 /* Upload a chip table (the rows of grid_tessellateexplode, MosaicExplode.scala:70-83,
  * ChipType.scala:17-29): cell id, owning polygon id, is_core, and the chip WKB
  * (big- or little-endian, Polygon / MultiPolygon / GeometryCollection of those;
@@ -643,7 +692,8 @@ int32_t mgpu_test_parse_number(const char* s, int32_t len, double* out);
  * 2 unsupported type, 3 empty. */
 /* Test hooks of the exact H3 route (h3_exact.h), host-side: the route's elementary
  * operations (fn codes as oracle/oracle.h orc_h3_elementary: correctly rounded libm and
- * emulated x87 long-double expressions), and point -> cell by the route alone. */
+ * emulated x87 long-double expressions; 14 and 15: the correctly rounded asin and atan of
+ * the cell-geometry route), and point -> cell by the route alone. */
 int32_t mgpu_test_h3_elementary_host(int32_t fn, const double* a, const double* b, int64_t n, double* out);
 int32_t mgpu_test_h3_route_host(const double* lon, const double* lat, int64_t n, int32_t res, int64_t* out_cell);
 /* The near-tie resolver of the synchronous calls (h3_glibc.cpp: the reference's libm and
@@ -653,6 +703,11 @@ int32_t mgpu_test_h3_glibc_host(const double* lon, const double* lat, int64_t n,
  * out_lonlat[20 n] (up to 10 vertices per cell), out_nverts[n], out_center[2 n]. */
 int32_t mgpu_test_h3_boundary_host(const int64_t* cells, int64_t n, double* out_lonlat, int32_t* out_nverts,
                                    double* out_center);
+/* The cell-geometry kernels' host twin: the code of mgpu_cells_to_boundaries / _centers /
+ * _area compiled for the host (no GPU).  Host pointers: out_xy[20 n], out_nverts[n],
+ * out_center[2 n] (optional; NaN for BNG), out_area[n] (optional). */
+int32_t mgpu_test_cell_geometry_host(int32_t index_system, const int64_t* cells, int64_t n, double* out_xy,
+                                     int32_t* out_nverts, double* out_center, double* out_area);
 /* TEST ONLY: an H3 cell's geometry as a core chip of it carries it (indexToGeometry,
  * H3IndexSystem.scala:103-112: the polar caps of makePoleGeometry, antimeridian cells
  * cut) as WKB into out[cap]; *out_len = its size (MGPU_E_CAPACITY when it exceeds cap). */

@@ -10,6 +10,9 @@
 //     pointToIndex         IndexSystem.scala:237; H3IndexSystem.scala:168-170; BNGIndexSystem.scala:284-298
 //     format / parse       H3IndexSystem.scala:218-228; BNGIndexSystem.scala:119-134, 440-442
 //     formatCellId         IndexSystem.scala:48-57
+//     indexToCenter / indexToBoundary / indexToGeometry / area
+//                          IndexSystem.scala:223, :239-245, :248-291; H3IndexSystem.scala:103-112, :230-237;
+//                          BNGIndexSystem.scala:418-431, :510-524
 //   IndexSystemFactory     core/index/IndexSystemFactory.scala:31-63
 //   grid_tessellateexplode MosaicExplode.scala:70-79 -> Mosaic.getChips (core/Mosaic.scala:22-99)
 //   st_contains            ST_Contains.scala:21-44 -> MosaicGeometryJTS.contains (MosaicGeometryJTS.scala:197)
@@ -119,6 +122,41 @@ class IndexSystem {
                      int64_t* out_dev, void* stream = nullptr, mgpu_stats* stats = nullptr) const {
     const int r = getResolution(resolution);
     check(mgpu_points_to_cells(ctx.get(), code(), r, x_dev, y_dev, n, out_dev, stream, stats));
+  }
+
+  // indexToCenter / indexToBoundary / indexToGeometry / area over a device column of cells
+  // (IndexSystem.scala:223, :239-245, :248-291; mgpu_cells_*): device pointers, `valid_dev`
+  // an optional Arrow bitmap read from bit valid_offset, `out_valid_dev` (optional) the rows'
+  // bitmap at bit 0.  The reference's scalar forms are a column of one.  A row that is not a
+  // cell id throws IllegalArgumentException.
+  // centres: lng to x_dev, lat to y_dev (degrees); BNG throws (NotImplementedError there)
+  void indexToCenter(GpuContext& ctx, const int64_t* cells_dev, int64_t n, double* x_dev, double* y_dev,
+                     const uint8_t* valid_dev = nullptr, int64_t valid_offset = 0, uint8_t* out_valid_dev = nullptr,
+                     void* stream = nullptr) const {
+    check(mgpu_cells_to_centers(ctx.get(), code(), cells_dev, valid_dev, valid_offset, n, x_dev, y_dev, out_valid_dev, stream));
+  }
+  // boundaries: row i has nverts_dev[i] (x, y) pairs at xy_dev[20 i ..], not closed
+  void indexToBoundary(GpuContext& ctx, const int64_t* cells_dev, int64_t n, double* xy_dev, int32_t* nverts_dev,
+                       const uint8_t* valid_dev = nullptr, int64_t valid_offset = 0, uint8_t* out_valid_dev = nullptr,
+                       void* stream = nullptr) const {
+    check(mgpu_cells_to_boundaries(ctx.get(), code(), cells_dev, valid_dev, valid_offset, n, xy_dev, nverts_dev,
+                                   out_valid_dev, stream));
+  }
+  // geometries as WKB: row i at out_dev[offsets_dev[i] .. offsets_dev[i + 1]); returns the bytes
+  // written (CapacityError.required when out_bytes is too small)
+  int64_t indexToGeometry(GpuContext& ctx, const int64_t* cells_dev, int64_t n, uint8_t* out_dev, int64_t out_bytes,
+                          int64_t* offsets_dev, const uint8_t* valid_dev = nullptr, int64_t valid_offset = 0,
+                          uint8_t* out_valid_dev = nullptr, void* stream = nullptr) const {
+    int64_t total = 0;
+    const int32_t st = mgpu_cells_boundary_wkb(ctx.get(), code(), cells_dev, valid_dev, valid_offset, n, out_dev, out_bytes,
+                                               offsets_dev, &total, out_valid_dev, stream);
+    check(st, total);
+    return total;
+  }
+  // areas in km^2
+  void area(GpuContext& ctx, const int64_t* cells_dev, int64_t n, double* area_dev, const uint8_t* valid_dev = nullptr,
+            int64_t valid_offset = 0, uint8_t* out_valid_dev = nullptr, void* stream = nullptr) const {
+    check(mgpu_cells_area(ctx.get(), code(), cells_dev, valid_dev, valid_offset, n, area_dev, out_valid_dev, stream));
   }
 
   virtual std::string format(int64_t id) const = 0;

@@ -48,6 +48,8 @@ EXPORTS = (
     "mgpu_pip_join_lookup",
     "mgpu_cell_agg_create", "mgpu_cell_agg_add_points", "mgpu_cell_agg_add_cells", "mgpu_cell_agg_add_counted",
     "mgpu_cell_agg_size", "mgpu_cell_agg_fetch", "mgpu_cell_agg_clear", "mgpu_cell_agg_destroy",
+    "mgpu_cells_to_centers", "mgpu_cells_to_boundaries", "mgpu_cells_boundary_wkb", "mgpu_cells_area",
+    "mgpu_test_cell_geometry_host",
 )
 MGPU_GEOM_WKB = 0
 MGPU_GEOM_WKT = 1
@@ -204,6 +206,11 @@ def lib():
         "mgpu_cell_agg_fetch": (I32, [P, P, I64, P, P, P, ctypes.POINTER(I64), P]),
         "mgpu_cell_agg_clear": (I32, [P, P, P]),
         "mgpu_cell_agg_destroy": (I32, [P]),
+        "mgpu_cells_to_centers": (I32, [P, I32, P, P, I64, I64, P, P, P, P]),
+        "mgpu_cells_to_boundaries": (I32, [P, I32, P, P, I64, I64, P, P, P, P]),
+        "mgpu_cells_boundary_wkb": (I32, [P, I32, P, P, I64, I64, P, I64, P, ctypes.POINTER(I64), P, P]),
+        "mgpu_cells_area": (I32, [P, I32, P, P, I64, I64, P, P, P]),
+        "mgpu_test_cell_geometry_host": (I32, [I32, P, I64, P, P, P, P]),
         "mgpu_ring_join": (I32, [P, I32, I32, I32, I32, P, P, I64, P, P, I64, I64, I32, ctypes.c_double, I64,
                                  ctypes.POINTER(I64), P, P, P, P]),
         "mgpu_ring_join_ex": (I32, [P, I32, I32, I32, I32, P, P, I64, P, P, I64, I64, I32, ctypes.c_double, I32,

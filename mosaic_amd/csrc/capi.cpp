@@ -1802,6 +1802,9 @@ int32_t mgpu_test_h3_elementary_host(int32_t fn, const double* a, const double* 
       case 11: r = X::x80_to_double(X::x80_add(X::x80_from_double(x), X::kXAp7Rot)); break;
       case 12: r = X::x80_cmp(X::x80_from_double(x), X::kXEpsilon) < 0 ? 1.0 : 0.0; break;
       case 13: r = X::x80_cmp(X::x80_from_double(x), X::kX2Pi) >= 0 ? 1.0 : 0.0; break;
+      // the cell-geometry route's additions (no oracle code: checked against asinl / atanl)
+      case 14: r = X::cr_asin(x); break;
+      case 15: r = X::cr_atan(x); break;
       default: return MGPU_E_INVALID_ARG;
     }
     out[i] = r;

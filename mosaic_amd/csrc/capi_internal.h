@@ -120,7 +120,8 @@ int32_t begin_call(mgpu_ctx* ctx);
 }  // namespace mgpu
 
 // capi.cpp, shared with cell_agg.hip: mgpu_points_to_cells' body (after begin_call; out_cell
-// a device column) and the context's scratch buffer, grown to at least `bytes`.
+// a device column) and the context's scratch buffer, grown to at least `bytes` (the latter
+// also holds cell_geom.hip's boundaries, lengths and counters).
 int32_t cells_impl(mgpu_ctx* ctx, int32_t is, int32_t res, const double* x, const double* y, int64_t n,
                    int64_t* out_cell, hipStream_t s, const uint8_t* valid, int64_t voff, mgpu_stats* stats);
 int32_t ensure_scratch(mgpu_ctx* ctx, size_t bytes);

@@ -227,6 +227,14 @@ MGPU_XD int x80_cmp(X80 a, X80 b) {
   return sa > 0 ? mag : -mag;
 }
 
+// (double)((long double)a OP c) through the emulation, on the host and the device alike
+MGPU_XD double em_add(double a, X80 c) { return x80_to_double(x80_add(x80_from_double(a), c)); }
+MGPU_XD double em_sub(double a, X80 c) { return x80_to_double(x80_add(x80_from_double(a), x80_neg(c))); }
+MGPU_XD double em_mul(double a, X80 c) { return x80_to_double(x80_mul(x80_from_double(a), c)); }
+MGPU_XD double em_div(double a, X80 c) { return x80_to_double(x80_div(x80_from_double(a), c)); }
+MGPU_XD bool em_lt(double a, X80 c) { return x80_cmp(x80_from_double(a), c) < 0; }
+MGPU_XD bool em_ge(double a, X80 c) { return x80_cmp(x80_from_double(a), c) >= 0; }
+
 // (double)((long double)a OP c).  On an x86-64 host `long double` IS the x87 format:
 // there the hardware does it (the chip-table builder runs these per cell vertex); the
 // device -- and the tests, through the x80_* functions -- use the emulation.
@@ -243,12 +251,12 @@ inline double ld_div(double a, X80 c) { return (double)((long double)a / x80_ld(
 inline bool ld_lt(double a, X80 c) { return (long double)a < x80_ld(c); }
 inline bool ld_ge(double a, X80 c) { return (long double)a >= x80_ld(c); }
 #else
-MGPU_XD double ld_add(double a, X80 c) { return x80_to_double(x80_add(x80_from_double(a), c)); }
-MGPU_XD double ld_sub(double a, X80 c) { return x80_to_double(x80_add(x80_from_double(a), x80_neg(c))); }
-MGPU_XD double ld_mul(double a, X80 c) { return x80_to_double(x80_mul(x80_from_double(a), c)); }
-MGPU_XD double ld_div(double a, X80 c) { return x80_to_double(x80_div(x80_from_double(a), c)); }
-MGPU_XD bool ld_lt(double a, X80 c) { return x80_cmp(x80_from_double(a), c) < 0; }
-MGPU_XD bool ld_ge(double a, X80 c) { return x80_cmp(x80_from_double(a), c) >= 0; }
+MGPU_XD double ld_add(double a, X80 c) { return em_add(a, c); }
+MGPU_XD double ld_sub(double a, X80 c) { return em_sub(a, c); }
+MGPU_XD double ld_mul(double a, X80 c) { return em_mul(a, c); }
+MGPU_XD double ld_div(double a, X80 c) { return em_div(a, c); }
+MGPU_XD bool ld_lt(double a, X80 c) { return em_lt(a, c); }
+MGPU_XD bool ld_ge(double a, X80 c) { return em_ge(a, c); }
 #endif
 
 // ------------------------------------------------------------------ double-double
@@ -433,6 +441,19 @@ MGPU_XD double cr_acos(double a) {
   }
   return dd_sub(DD{kPio2_1, kPio2_2}, dd_asin_small(DD{a, 0.0})).hi;
 }
+// asin: the series' range directly; beyond it asin s = pi/2 - 2 asin sqrt((1 - |s|) / 2)
+MGPU_XD double cr_asin(double a) {
+  if (!(a >= -1.0 && a <= 1.0)) return (a - a) / (a - a);
+  const double m = fabs(a);
+  if (m <= 0.75) return m == 0.0 ? a : dd_asin_small(DD{a, 0.0}).hi;
+  const double d = (1.0 - m) * 0.5;  // exact (Sterbenz)
+  double r = kPio2_1;
+  if (d != 0.0) {
+    const DD h = dd_asin_small(dd_sqrt(DD{d, 0.0}));
+    r = dd_sub(DD{kPio2_1, kPio2_2}, DD{2.0 * h.hi, 2.0 * h.lo}).hi;
+  }
+  return a < 0.0 ? -r : r;
+}
 MGPU_XD double cr_atan2(double y, double x) {
   const double t0 = atan2(y, x);
   if (!isfinite(x) || !isfinite(y) || (x == 0.0 && y == 0.0) || t0 == 0.0) return t0;
@@ -447,6 +468,7 @@ MGPU_XD double cr_atan2(double y, double x) {
   }
   return t.hi;
 }
+MGPU_XD double cr_atan(double r) { return cr_atan2(r, 1.0); }
 
 }  // namespace exact
 }  // namespace mgpu

@@ -203,6 +203,8 @@ hipError_t launch_decode_internal(const int32_t* type_id, const int64_t* row_par
 hipError_t launch_decode_points(int format, const uint8_t* data, const void* offsets, int off32, const uint8_t* valid,
                                 int64_t voff, int64_t n, double* x, double* y, unsigned long long* counters,
                                 hipStream_t s);
+// exclusive scan of v[0, n) in place (one workgroup: per-chunk totals of a two-level scan)
+hipError_t launch_scan_sums(int64_t* v, int64_t n, hipStream_t s);
 // AND of two validity bitmaps (either may be null) into out (bit offset 0), n bits
 hipError_t launch_valid_and(const uint8_t* a, int64_t aoff, const uint8_t* b, int64_t boff, int64_t n, uint8_t* out,
                             hipStream_t s);

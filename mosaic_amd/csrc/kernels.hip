@@ -2430,6 +2430,12 @@ hipError_t launch_kring_write(int is, const int64_t* cells, int64_t n, int k, in
   return hipGetLastError();
 }
 
+hipError_t launch_scan_sums(int64_t* v, int64_t n, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(kScan), 0, s, v, n);
+  return hipGetLastError();
+}
+
 hipError_t launch_format_cells(int is, const int64_t* cells, int64_t n, char* out, int64_t out_bytes,
                                int64_t* offsets, int64_t* chunk, unsigned long long* counters, hipStream_t s) {
   hipError_t e = hipMemsetAsync(offsets, 0, sizeof(int64_t), s);

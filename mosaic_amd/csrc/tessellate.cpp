@@ -54,6 +54,7 @@
 #include "bng_core.h"
 #include "h3_core.h"
 #include "h3_boundary.h"
+#include "cell_geom.h"
 #include "jts_buffer.h"
 #include "jts_overlay.h"
 #include "parallel.h"
@@ -336,10 +337,9 @@ struct CachedVertex {
 // degrees, closed, ccw; the cell holding a pole as the cap between its boundary and
 // the pole (makePoleGeometry, :361-384); a cell across the antimeridian cut into its
 // western and eastern parts (makeSafeGeometry / crossesAntiMeridian, :386-410, :258-262)
-std::vector<std::vector<Pt>> h3_cell_rings(uint64_t id, int res) {
-  std::vector<Pt> b;
-  for (auto& v : mgpu::h3b::cell_boundary(id, CachedVertex()))
-    b.push_back({mgpu::h3b::to_degrees(v.lon), mgpu::h3b::to_degrees(v.lat)});
+// (the boundary -> rings part: `b` the h3ToGeoBoundary vertices in degrees, not closed;
+// shared with the cell-geometry entries, whose boundaries the device computes)
+std::vector<std::vector<Pt>> h3_boundary_rings(uint64_t id, int res, std::vector<Pt> b) {
   const int pole = id == pole_cell(true, res) ? 1 : (id == pole_cell(false, res) ? -1 : 0);
   if (pole) return {pole_cap(b, pole > 0)};
   double lo = INFINITY, hi = -INFINITY;
@@ -368,6 +368,13 @@ std::vector<std::vector<Pt>> h3_cell_rings(uint64_t id, int res) {
     out.push_back(std::move(e));
   }
   return out;
+}
+
+std::vector<std::vector<Pt>> h3_cell_rings(uint64_t id, int res) {
+  std::vector<Pt> b;
+  for (auto& v : mgpu::h3b::cell_boundary(id, CachedVertex()))
+    b.push_back({mgpu::h3b::to_degrees(v.lon), mgpu::h3b::to_degrees(v.lat)});
+  return h3_boundary_rings(id, res, std::move(b));
 }
 
 struct Grid {
@@ -1385,6 +1392,23 @@ double h3_buffer_radius(const Polygon& poly, int res) {
 
 }  // namespace
 
+namespace mgpu {
+namespace cellgeom {
+
+void h3_special_cell_wkb(uint64_t cell, const double* boundary, int nv, std::vector<uint8_t>& out) {
+  const int res = (int)((cell >> 52) & 15);
+  std::vector<Pt> b;
+  for (int v = 0; v < nv; v++) b.push_back({boundary[2 * v], boundary[2 * v + 1]});
+  auto rings = h3_boundary_rings(cell, res, std::move(b));
+  if (cell == pole_cell(false, res)) rings = reversed(rings);  // as H3Grid::cw_ring
+  write_cell_wkb(rings, out);
+}
+
+uint64_t h3_pole_cell(bool north, int res) { return pole_cell(north, res); }
+
+}  // namespace cellgeom
+}  // namespace mgpu
+
 extern "C" {
 
 int32_t mgpu_tessellate(int32_t index_system, int32_t res, int64_t n_polys, const int32_t* polygon_id,
@@ -1688,6 +1712,43 @@ int32_t mgpu_test_h3_boundary_host(const int64_t* cells, int64_t n, double* out_
     const auto c = mgpu::h3b::cell_center(h);
     out_center[2 * i] = mgpu::h3b::to_degrees(c.lon);
     out_center[2 * i + 1] = mgpu::h3b::to_degrees(c.lat);
+  }
+  return MGPU_OK;
+}
+
+// The cell-geometry kernels' host twin: h3_boundary.h under its correctly rounded policy
+// and cell_geom.h's area, compiled for the host (no FMA contraction: the device's bits).
+int32_t mgpu_test_cell_geometry_host(int32_t index_system, const int64_t* cells, int64_t n, double* out_xy,
+                                     int32_t* out_nverts, double* out_center, double* out_area) {
+  namespace CG = mgpu::cellgeom;
+  using M = mgpu::h3b::CrMath;
+  if (index_system != MGPU_H3 && index_system != MGPU_BNG)
+    return mgpu::set_error(MGPU_E_INVALID_ARG, "unknown index system %d (0 = H3, 1 = BNG)", index_system);
+  if (n < 0 || (n > 0 && (!cells || !out_xy || !out_nverts)))
+    return mgpu::set_error(MGPU_E_INVALID_ARG, "cell geometry (host): bad arguments");
+  const double nan = std::nan("");
+  for (int64_t i = 0; i < n; i++) {
+    double* xy = out_xy + i * CG::kRowDoubles;
+    if (index_system == MGPU_BNG) {
+      double area;
+      if (!CG::bng_cell(cells[i], xy, &area)) return mgpu::set_error(MGPU_E_INVALID_ARG, "cell geometry: not a BNG cell id");
+      out_nverts[i] = 4;
+      if (out_center) out_center[2 * i] = out_center[2 * i + 1] = nan;
+      if (out_area) out_area[i] = area;
+      continue;
+    }
+    const uint64_t h = (uint64_t)cells[i];
+    if (!mgpu::h3b::is_valid_cell(h)) return mgpu::set_error(MGPU_E_INVALID_ARG, "cell geometry: not an H3 cell id");
+    const auto b = mgpu::h3b::cell_boundary_m<M>(h, mgpu::h3b::VertexGeoT<M>());
+    out_nverts[i] = (int32_t)b.size();
+    for (size_t v = 0; v < b.size(); v++) {
+      xy[2 * v] = mgpu::h3b::to_degrees(b[v].lon);
+      xy[2 * v + 1] = mgpu::h3b::to_degrees(b[v].lat);
+    }
+    const auto c = mgpu::h3b::cell_center_m<M>(h);
+    const double cx = mgpu::h3b::to_degrees(c.lon), cy = mgpu::h3b::to_degrees(c.lat);
+    if (out_center) out_center[2 * i] = cx, out_center[2 * i + 1] = cy;
+    if (out_area) out_area[i] = CG::h3_area_km2<M>(xy, (int)b.size(), cx, cy);
   }
   return MGPU_OK;
 }

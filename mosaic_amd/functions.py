@@ -219,6 +219,35 @@ def grid_cellkloop(cells, k, index_system, ctx=None, stream=None):
     return grid_cellkring(cells, k, index_system, loop_only=True, ctx=ctx, stream=stream)
 
 
+def grid_boundaryaswkb(cells, index_system, valid=None, valid_offset=0, ctx=None, stream=None):
+    """grid_boundaryaswkb (IndexGeometry.scala:65-75 -> IndexSystem.indexToGeometry, as WKB)
+    over a device int64 column, on the GPU (H3, BNG).  Returns (bytes uint8 tensor, offsets
+    int64 tensor of n + 1) like IndexSystem.format_device: row i is
+    bytes[offsets[i]:offsets[i + 1]] -- a Polygon of the cell's closed boundary; an H3 cell
+    holding a pole is the reference's polar cap, one across the antimeridian its two parts.
+    ``valid``: an optional Arrow validity bitmap (uint8 device tensor) read from bit
+    ``valid_offset``; null rows are empty, and the rows' bitmap (bit offset 0) comes back as
+    a third element.  A non-null row that is not a cell id raises IllegalArgumentException."""
+    return index_system.cells_boundary_wkb(cells, valid=valid, valid_offset=valid_offset, ctx=ctx, stream=stream)
+
+
+def grid_boundary(cells, fmt, index_system, valid=None, valid_offset=0, ctx=None, stream=None):
+    """grid_boundary(cell, format) (IndexGeometry.scala:65-75).  The device path writes WKB
+    only: "WKT", "GEOJSON" and "COORDS" need Java's Double.toString and raise
+    IllegalArgumentException."""
+    if str(fmt).upper() != "WKB":
+        raise N.IllegalArgumentException(N.MGPU_E_INVALID_ARG, "grid_boundary: format %r is not on the device path "
+                                         "(WKB only)" % (fmt,))
+    return grid_boundaryaswkb(cells, index_system, valid=valid, valid_offset=valid_offset, ctx=ctx, stream=stream)
+
+
+def grid_cellarea(cells, index_system, valid=None, valid_offset=0, ctx=None, stream=None):
+    """grid_cellarea (CellArea.scala -> IndexSystem.area) over a device int64 column, on the
+    GPU: km^2 as a float64 device tensor (NaN in null rows; with ``valid`` the rows' bitmap
+    as a second element)."""
+    return index_system.cells_area(cells, valid=valid, valid_offset=valid_offset, ctx=ctx, stream=stream)
+
+
 def grid_tessellateexplode(polygons, resolution, keep_core_geometries=True, index_system=None):
     """Chip rows (is_core, index_id, wkb) of every polygon -> ChipTable (host columns)."""
     return tessellate(polygons, index_system or _H3, resolution, keep_core_geometries)

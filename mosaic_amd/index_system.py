@@ -136,6 +136,112 @@ class IndexSystem:
         return [int(v) for v in ids.cpu().tolist()]
 
 
+    # -- cell -> geometry (mgpu_cells_*, HIP) ------------------------------
+    def _cell_column(self, cells, valid, valid_offset, ctx, stream):
+        import torch
+        from .context import default_context
+        if cells.dtype != torch.int64 or not cells.is_cuda or cells.dim() != 1:
+            raise IllegalArgumentException(N.MGPU_E_INVALID_ARG, "cells must be a 1-D int64 device tensor")
+        cells = cells.contiguous()
+        n = cells.numel()
+        if valid is not None and (valid.dtype != torch.uint8 or valid.device != cells.device or not valid.is_contiguous()
+                                  or valid_offset < 0 or valid.numel() * 8 < valid_offset + n):
+            raise IllegalArgumentException(N.MGPU_E_INVALID_ARG, "valid must be a contiguous uint8 bitmap of at least "
+                                           "valid_offset + n bits on the cells' device")
+        ctx = ctx or default_context(cells.device)
+        s = stream if stream is not None else torch.cuda.current_stream(cells.device).cuda_stream
+        out_valid = None if valid is None else torch.empty((n + 7) // 8 + 1, dtype=torch.uint8, device=cells.device)
+        return cells, n, ctx, s, (None if valid is None else valid.data_ptr()), out_valid
+
+    def cells_to_centers(self, cells, valid=None, valid_offset=0, ctx=None, stream=None):
+        """Batch IndexSystem.indexToCenter (IndexSystem.scala:239) over a device int64 column:
+        (lng, lat) float64 device tensors, NaN in null rows; with ``valid`` (an Arrow bitmap
+        read from bit ``valid_offset``) also the rows' bitmap at bit offset 0."""
+        import torch
+        cells, n, ctx, s, vp, ov = self._cell_column(cells, valid, valid_offset, ctx, stream)
+        x = torch.empty(max(n, 1), dtype=torch.float64, device=cells.device)
+        y = torch.empty(max(n, 1), dtype=torch.float64, device=cells.device)
+        N.check(N.lib().mgpu_cells_to_centers(ctx.handle, self.code, cells.data_ptr(), vp, valid_offset, n, x.data_ptr(),
+                                              y.data_ptr(), None if ov is None else ov.data_ptr(), s))
+        return (x[:n], y[:n]) if ov is None else (x[:n], y[:n], ov[:(n + 7) // 8])
+
+    def cells_to_boundaries(self, cells, valid=None, valid_offset=0, ctx=None, stream=None):
+        """Batch IndexSystem.indexToBoundary (IndexSystem.scala:243; BNG: the corners of
+        indexToGeometry): (xy float64 (n, 10, 2), nverts int32 (n)) device tensors -- row i's
+        boundary is xy[i, :nverts[i]], (x, y) = (lng, lat) for H3, not closed; a null row has
+        0 vertices.  With ``valid`` also the rows' bitmap."""
+        import torch
+        cells, n, ctx, s, vp, ov = self._cell_column(cells, valid, valid_offset, ctx, stream)
+        xy = torch.zeros((max(n, 1), 10, 2), dtype=torch.float64, device=cells.device)
+        nv = torch.empty(max(n, 1), dtype=torch.int32, device=cells.device)
+        N.check(N.lib().mgpu_cells_to_boundaries(ctx.handle, self.code, cells.data_ptr(), vp, valid_offset, n,
+                                                 xy.data_ptr(), nv.data_ptr(), None if ov is None else ov.data_ptr(), s))
+        return (xy[:n], nv[:n]) if ov is None else (xy[:n], nv[:n], ov[:(n + 7) // 8])
+
+    def cells_boundary_wkb(self, cells, valid=None, valid_offset=0, ctx=None, stream=None):
+        """Batch IndexSystem.indexToGeometry as WKB (IndexGeometry.scala:65-75): (bytes uint8
+        tensor, offsets int64 tensor of n + 1), row i = bytes[offsets[i]:offsets[i + 1]]
+        (empty for a null row).  With ``valid`` also the rows' bitmap."""
+        import ctypes
+        import torch
+        cells, n, ctx, s, vp, ov = self._cell_column(cells, valid, valid_offset, ctx, stream)
+        off = torch.empty(n + 1, dtype=torch.int64, device=cells.device)
+        cap = 125 * n + 1024  # a hexagon's row; grown to the reported size when the column needs more
+        tot = ctypes.c_int64()
+        while True:
+            out = torch.empty(cap, dtype=torch.uint8, device=cells.device)
+            st = N.lib().mgpu_cells_boundary_wkb(ctx.handle, self.code, cells.data_ptr(), vp, valid_offset, n,
+                                                 out.data_ptr(), cap, off.data_ptr(), ctypes.byref(tot),
+                                                 None if ov is None else ov.data_ptr(), s)
+            if st != N.MGPU_E_CAPACITY or tot.value <= cap:
+                break
+            cap = tot.value
+        N.check(st, required=tot.value)
+        return (out[:tot.value], off) if ov is None else (out[:tot.value], off, ov[:(n + 7) // 8])
+
+    def cells_area(self, cells, valid=None, valid_offset=0, ctx=None, stream=None):
+        """Batch IndexSystem.area (IndexSystem.scala:248-289, BNGIndexSystem.scala:510-516):
+        km^2 as a float64 device tensor, NaN in null rows.  With ``valid`` also the rows' bitmap."""
+        import torch
+        cells, n, ctx, s, vp, ov = self._cell_column(cells, valid, valid_offset, ctx, stream)
+        a = torch.empty(max(n, 1), dtype=torch.float64, device=cells.device)
+        N.check(N.lib().mgpu_cells_area(ctx.handle, self.code, cells.data_ptr(), vp, valid_offset, n, a.data_ptr(),
+                                        None if ov is None else ov.data_ptr(), s))
+        return a[:n] if ov is None else (a[:n], ov[:(n + 7) // 8])
+
+    def _one_cell(self, index):
+        import torch
+        from .context import default_context
+        ctx = default_context()
+        cell = self.parse(index) if isinstance(index, str) else int(index)
+        return torch.tensor([cell], dtype=torch.int64, device=ctx.device), ctx
+
+    def index_to_center(self, index):
+        """IndexSystem.indexToCenter(index) (IndexSystem.scala:239-241): (lat, lng), as the
+        reference's Coordinates; a string id goes through parse."""
+        cells, ctx = self._one_cell(index)
+        x, y = self.cells_to_centers(cells, ctx=ctx)
+        return (float(y[0].item()), float(x[0].item()))
+
+    def index_to_boundary(self, index):
+        """IndexSystem.indexToBoundary(index) (IndexSystem.scala:243-245): the list of
+        (lat, lng) Coordinates, not closed."""
+        cells, ctx = self._one_cell(index)
+        xy, nv = self.cells_to_boundaries(cells, ctx=ctx)
+        return [(float(p[1]), float(p[0])) for p in xy[0, :int(nv[0].item())].cpu().tolist()]
+
+    def index_to_geometry(self, index):
+        """IndexSystem.indexToGeometry(index) (IndexSystem.scala:223) as WKB bytes."""
+        cells, ctx = self._one_cell(index)
+        w, _ = self.cells_boundary_wkb(cells, ctx=ctx)
+        return bytes(w.cpu().numpy().tobytes())
+
+    def area(self, index):
+        """IndexSystem.area(index) (IndexSystem.scala:248-291), km^2."""
+        cells, ctx = self._one_cell(index)
+        return float(self.cells_area(cells, ctx=ctx)[0].item())
+
+
 def _check_points(x, y):
     if x.dtype != y.dtype or str(x.dtype) != "torch.float64":
         raise IllegalArgumentException(N.MGPU_E_INVALID_ARG, "coordinates must be float64 tensors")
@@ -234,6 +340,14 @@ class BNGIndexSystem(IndexSystem):
         N.check(N.lib().mgpu_bng_parse(buf.ctypes.data, off.ctypes.data, len(enc), out.ctypes.data),
                 "not a BNG cell id")
         return out
+
+    def index_to_center(self, index):
+        """BNGIndexSystem.indexToCenter (BNGIndexSystem.scala:518-520) throws NotImplementedError."""
+        raise NotImplementedError
+
+    def index_to_boundary(self, index):
+        """BNGIndexSystem.indexToBoundary (BNGIndexSystem.scala:522-524) throws NotImplementedError."""
+        raise NotImplementedError
 
     def format(self, cell_id):
         return self.format_many([cell_id])[0]
