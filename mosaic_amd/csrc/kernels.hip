@@ -18,6 +18,7 @@
 // Nothing here is a dense contraction, so MFMA is not used.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include <map>
 #include <mutex>
@@ -1653,7 +1654,11 @@ __global__ __launch_bounds__(kBlock) void pip_mixed_fix_kernel(JoinArgs a) {
 // point its rank in the chunk's mixed list (classify_kernel ranks them in point order
 // too), a second scan of the pair counts each thread's first output slot.  The chunk's
 // pairs are one contiguous output range: staged in LDS (polygon id, point) a window of
-// kEmitWin pairs at a time, then written by consecutive lanes.
+// kEmitWin pairs at a time, then written by consecutive lanes.  The per-item passes have
+// two forms, chosen per wave (split_emit_kernel: "the fast form"): straight-line predicated
+// code when every item of the wave gives at most one pair whose polygon is in LDS, the
+// general loops otherwise.  (Round 9, profiles/r9/: the general loops' exec-mask
+// bookkeeping was 1,054 of a wave's 2,000 instructions on C2; the fast form issues 187.)
 // A workgroup barrier that orders LDS only: __syncthreads() also waits for the wave's
 // outstanding global loads and stores (its release fence), which would hold the emit
 // kernels' output stores and the next chunk's prefetched loads at every barrier.
@@ -1702,8 +1707,8 @@ __device__ __forceinline__ uint32_t emit_swz(uint32_t q) { return MGPU_EMIT_SWZ 
 #ifndef MGPU_EMIT_NT_OTHER
 #define MGPU_EMIT_NT_OTHER 0
 #endif
-// waves per SIMD asked of the compiler.  split_emit_kernel<H3> takes 57 VGPRs (8 waves)
-// and 16,416 B of LDS plus its class table -- 9 workgroups, 36 waves, per CU: the
+// waves per SIMD asked of the compiler.  split_emit_kernel<H3> takes 60 VGPRs (8 waves)
+// and 16,800 B of LDS plus its class table -- 9 workgroups, 36 waves, per CU: the
 // registers set its occupancy, 8.  (Round 3's "8: 64 VGPRs, spills" forced the attribute
 // on a source that carried its decoded codes, see emit_forget.)
 #ifndef MGPU_EMIT_WAVES
@@ -1732,6 +1737,8 @@ __host__ __device__ inline uint32_t emit_cls_staged(const ChipTableView& t) {
   const uint32_t n = t.raster_ncls < t.raster_pc[0] ? t.raster_ncls : t.raster_pc[0];
   return n < (uint32_t)kEmitCls ? n : (uint32_t)kEmitCls;
 }
+constexpr int kEmitTrash = 64;  // staging slots past the window, one per lane, written and never read (the fast form)
+typedef uint32_t __attribute__((may_alias)) lds_u32;  // a 32-bit word of either LDS table (s_cp, s_mr)
 // The thread's code words, made opaque to the compiler before each pass over them: it
 // otherwise decodes the 16 codes (and their compares, the point indices, the class
 // lookups) once, ahead of the passes and of the window loop, and carries them all -- 96
@@ -1750,8 +1757,10 @@ __global__ __launch_bounds__(kClsBlock) __attribute__((amdgpu_waves_per_eu(IS ==
   const JoinArgs& a = sa.j;
   const ChipTableView& t = a.chips;
   __shared__ uint32_t s_w[2][kClsBlock / 64];
-  __shared__ uint32_t s_poly[kEmitWin];  // staging: polygon id
-  __shared__ uint16_t s_pt[kEmitWin];    // staging: point of the chunk
+  // (kEmitTrash slots past the window: where the fast form's lanes write an item that gives
+  // no pair, or none in this window -- one slot per lane, never read)
+  __shared__ uint32_t s_poly[kEmitWin + kEmitTrash];  // staging: polygon id
+  __shared__ uint16_t s_pt[kEmitWin + kEmitTrash];    // staging: point of the chunk
   // mixed results: first chip | mask << 32; a one-chip match as its polygon | 1 << 32
   __shared__ uint64_t s_mr[MGPU_EMIT_MR ? kEmitMres : 1];
   extern __shared__ int32_t s_cp[];  // [emit_cls_staged(chips)]: dynamic LDS, sized at launch
@@ -1814,28 +1823,92 @@ __global__ __launch_bounds__(kClsBlock) __attribute__((amdgpu_waves_per_eu(IS ==
   uint32_t all_mixed;
   const uint32_t rank0 = chunk_excl_scan(nmix, s_w[0], &all_mixed);
   uint32_t npair = 0, r = rank0;
-  emit_forget(cw);
+  // The fast form (H3).  An item is "fast" when it gives at most one pair whose polygon is
+  // in LDS: an empty code, a class of the staged table (one match), or a mixed point whose
+  // answer is staged and has at most one match.  Its count and, below, its staging are
+  // straight-line code: the LDS reads and writes are unconditional, selects stand for the
+  // branches, and the rank and the slot advance by predicates -- no exec mask is saved or
+  // branched around per item.  emits: bit k = item k gives its pair.  A wave with any
+  // other item (wave_slow, wave-uniform) takes the general loops for all its lanes; both
+  // forms fill the same slots, so the waves of a workgroup may differ.
+  uint32_t emits = 0;
+  bool wave_slow = true;
+  if constexpr (IS == MGPU_H3) {
+    uint32_t cmax = 0, pmax = 0;  // the largest non-mixed code; the most matches of a mixed answer
+    emit_forget(cw);
 #pragma unroll
-  for (int k = 0; k < kClsItems; k++) {
-    const Code c = code(k);
-    if (c == kMixed)
-      npair += __popc((uint32_t)(mres(r++) >> 32));
-    else if (c != 0) {
-      if (IS == MGPU_H3)  // the match count from the class order (raster_pc)
-        npair += c < t.raster_pc[0]   ? 1u
-                 : c < t.raster_pc[1] ? 2u
-                 : c < t.raster_pc[2] ? 3u
-                 : c < t.raster_pc[3] ? 4u
-                                      : (uint32_t)__popc((uint32_t)(pure(c) >> 32));
-      else
-        npair += (uint32_t)__popc((uint32_t)c & 0xFFu);
+    for (int k = 0; k < kClsItems; k++) {
+      const uint32_t c = code(k);
+      const bool mixed = c == (uint32_t)kMixed;
+      const uint32_t rs = kMr ? (r < kMr - 1 ? r : kMr - 1) : 0u;  // (a rank past the staged ones: the wave is slow)
+      const uint32_t pm = (uint32_t)__popc((uint32_t)(s_mr[rs] >> 32));
+      const uint32_t cnt = mixed ? pm : (uint32_t)(c != 0);
+      pmax = mixed && pm > pmax ? pm : pmax;
+      cmax = !mixed && c > cmax ? c : cmax;
+      npair += cnt;
+      emits |= (cnt & 1u) << k;
+      r += mixed;
+    }
+    const bool slow = cmax >= ncp || pmax > 1 || (nmix != 0 && r > kMr);
+    wave_slow = __any(slow);
+  }
+  if (wave_slow) {
+    npair = 0, r = rank0;
+    emit_forget(cw);
+#pragma unroll
+    for (int k = 0; k < kClsItems; k++) {
+      const Code c = code(k);
+      if (c == kMixed)
+        npair += __popc((uint32_t)(mres(r++) >> 32));
+      else if (c != 0) {
+        if (IS == MGPU_H3)  // the match count from the class order (raster_pc)
+          npair += c < t.raster_pc[0]   ? 1u
+                   : c < t.raster_pc[1] ? 2u
+                   : c < t.raster_pc[2] ? 3u
+                   : c < t.raster_pc[3] ? 4u
+                                        : (uint32_t)__popc((uint32_t)(pure(c) >> 32));
+        else
+          npair += (uint32_t)__popc((uint32_t)c & 0xFFu);
+      }
     }
   }
   uint32_t total;
   const uint32_t off0 = chunk_excl_scan(npair, s_w[1], &total);
+  total = __builtin_amdgcn_readfirstlane(total);  // (the same in every lane: the window loop is uniform)
   const uint64_t base = sa.chunk_off[blockIdx.x];
+  // the fast form's staging pass over window w0; kOneWin: the chunk's pairs fit one window
+  // (w0 = 0), so no slot is tested against it
+  auto stage_fast = [&](auto one_win, uint32_t w0) {
+    constexpr bool kOneWin = decltype(one_win)::value;
+    uint32_t q = off0 - w0;  // (the slot in the window; wraps below it: the unsigned test fails)
+    r = rank0;
+    const uint32_t trash = (uint32_t)kEmitWin + (threadIdx.x & 63u);
+    const uint32_t pt0 = threadIdx.x * kClsItems;
+    uint32_t em = emits;
+    emit_forget(cw);
+    asm volatile("" : "+v"(q), "+v"(em));  // (as the codes: the 16 slots are not computed ahead of the window loop and carried)
+#pragma unroll
+    for (int k = 0; k < kClsItems; k++) {
+      const uint32_t c = code(k);
+      const bool mixed = c == (uint32_t)kMixed;
+      // the polygon: the staged answer's low word, or the class's (c < ncp, r < kMr here)
+      const lds_u32* src = mixed ? (const lds_u32*)&s_mr[r] : (const lds_u32*)&s_cp[c];
+      const uint32_t poly = *src;
+      const bool e = (em >> k) & 1u;
+      const uint32_t slot = e && (kOneWin || q < (uint32_t)kEmitWin) ? emit_swz(q) : trash;
+      s_poly[slot] = poly;
+      s_pt[slot] = (uint16_t)(pt0 + k);
+      q += e;
+      r += mixed;
+    }
+  };
   for (uint32_t w0 = 0; w0 < total; w0 += kEmitWin) {
-    if (off0 < w0 + kEmitWin && off0 + npair > w0) {
+    if (!wave_slow) {
+      if (total <= (uint32_t)kEmitWin)
+        stage_fast(std::true_type{}, 0u);
+      else if (__any(off0 < w0 + kEmitWin && off0 + npair > w0))
+        stage_fast(std::false_type{}, w0);
+    } else if (off0 < w0 + kEmitWin && off0 + npair > w0) {
       uint32_t q = off0;
       r = rank0;
       emit_forget(cw);
