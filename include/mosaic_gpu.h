@@ -139,6 +139,9 @@ int32_t mgpu_ctx_destroy(mgpu_ctx* ctx);
  *                     per launch as fit its 256 MB of scratch; 1..2^31-1: at most this many
  *                     (and still at most what fits; a test hook: a small value makes the
  *                     fallback run in many batches)
+ *   "polyfill_slab"   mgpu_grid_polyfill processes its lattice samples in slabs of at most this
+ *                     many (default 2^24, 256..2^28), whose matches wait in context scratch for
+ *                     the gather; a slab boundary does not change the output
  *   "raster", "raster_bng", "raster_sub", "raster_milli"
  *                     the chip-table builder of mgpu_chips_upload on this context
  *                     (mgpu_build_opts below)
@@ -291,6 +294,33 @@ int32_t mgpu_cells_boundary_wkb(mgpu_ctx* ctx, int32_t index_system, const int64
  * coordinates above; BNGIndexSystem.scala:510-516: (edge / 1000)^2).  Queued on `stream`. */
 int32_t mgpu_cells_area(mgpu_ctx* ctx, int32_t index_system, const int64_t* cells, const uint8_t* valid,
                         int64_t valid_offset, int64_t n, double* out_area_km2, uint8_t* out_valid, void* stream);
+
+/* IndexSystem.polyfill (IndexSystem.scala:166; H3IndexSystem.scala:134-154; BNGIndexSystem.scala:185-209),
+ * grid_polyfill (expressions/index/Polyfill.scala) over a polygon set: for polygon p, every cell at
+ * `res` whose centre lies in p's interior (the documented definition; docs/source/api/
+ * spatial-indexing.rst:191-220).  H3: the centre is h3ToGeo in degrees on the correctly rounded
+ * route of mgpu_cells_to_centers; BNG: JTS Centroid of the ring of indexToGeometry's corners.
+ * Containment is planar JTS PointLocator (RayCrossingCounter per ring: inside the shell and
+ * outside every hole of some part; a centre on the boundary is not contained).  Two documented
+ * differences from the reference: it returns the full set (the reference's flood fill / BFS can
+ * miss a matching cell that no chain of matching neighbours joins to a seed), and the H3 centres
+ * are the correctly rounded ones (within 1e-12 degrees of glibc's).
+ * Geometry: host pointers, the layout of mgpu_tessellate (rings closed, at least 4 points).
+ * Output: device pointers; polygon p's cells are out_cells[out_offsets[p] .. out_offsets[p+1]),
+ * in the order of the lattice the call lays over p's bounding box (row by row from the south-west;
+ * deterministic, not the reference's hash-set order); no cell twice; a polygon without parts
+ * gives an empty list.  *out_total = cells needed, MGPU_E_CAPACITY when above `capacity`
+ * (offsets are still written).  Synchronises `stream`.
+ * MGPU_E_RESOLUTION as mgpu_check_resolution; MGPU_E_INVALID_ARG: non-finite coordinates, H3
+ * coordinates outside [-180, 180] x [-90, 90], a ring of fewer than 4 points or not closed, a
+ * polygon whose lattice would exceed 2^31 - 1 samples; MGPU_E_UNSUPPORTED: an H3 polygon whose
+ * bounding box spans 180 degrees of longitude or more; MGPU_E_INTERNAL: the H3 lattice's
+ * certificate failed at every spacing tried.
+ * Option "polyfill_slab" (context): the samples whose matches are held in scratch at a time. */
+int32_t mgpu_grid_polyfill(mgpu_ctx* ctx, int32_t index_system, int32_t res, int64_t n_polys,
+                           const int64_t* poly_part_off, const int64_t* part_ring_off, const int64_t* ring_off,
+                           const double* xy, int64_t* out_cells, int64_t capacity, int64_t* out_offsets,
+                           int64_t* out_total, void* stream);
 
 /* Upload a chip table (the rows of grid_tessellateexplode, MosaicExplode.scala:70-83,
  * ChipType.scala:17-29): cell id, owning polygon id, is_core, and the chip WKB
@@ -708,6 +738,17 @@ int32_t mgpu_test_h3_boundary_host(const int64_t* cells, int64_t n, double* out_
  * out_center[2 n] (optional; NaN for BNG), out_area[n] (optional). */
 int32_t mgpu_test_cell_geometry_host(int32_t index_system, const int64_t* cells, int64_t n, double* out_xy,
                                      int32_t* out_nverts, double* out_center, double* out_area);
+/* TEST ONLY: mgpu_grid_polyfill's host twin -- the same plan walked by the same code on the
+ * host (no GPU), host pointers throughout; the same lists in the same order. */
+int32_t mgpu_test_grid_polyfill_host(int32_t index_system, int32_t res, int64_t n_polys, const int64_t* poly_part_off,
+                                     const int64_t* part_ring_off, const int64_t* ring_off, const double* xy,
+                                     int64_t* out_cells, int64_t capacity, int64_t* out_offsets, int64_t* out_total);
+/* TEST ONLY (and tools/polyfill_time.py): figures of the last mgpu_grid_polyfill or
+ * mgpu_test_grid_polyfill_host call made on the CALLING THREAD (thread-local state, overwritten
+ * by either entry; zeros before the first call): out8 = lattice samples, tiles, certificate
+ * failures over all attempts, attempts (1 = the first spacing held), device microseconds of the
+ * last attempt's launches between two events on its stream (the host twin: 0), 0, 0, 0. */
+int32_t mgpu_test_grid_polyfill_last(int64_t* out8);
 /* TEST ONLY: an H3 cell's geometry as a core chip of it carries it (indexToGeometry,
  * H3IndexSystem.scala:103-112: the polar caps of makePoleGeometry, antimeridian cells
  * cut) as WKB into out[cap]; *out_len = its size (MGPU_E_CAPACITY when it exceeds cap). */

@@ -159,6 +159,21 @@ class IndexSystem {
     check(mgpu_cells_area(ctx.get(), code(), cells_dev, valid_dev, valid_offset, n, area_dev, out_valid_dev, stream));
   }
 
+  // polyfill(geometry, resolution) over a polygon set (IndexSystem.scala:166; mgpu_grid_polyfill): the
+  // geometry as host arrays in mgpu_tessellate's layout, the cells to out_cells_dev[capacity] and polygon
+  // p's range to offsets_dev[p .. p + 1] (device); returns the cells needed (CapacityError.required when
+  // `capacity` is too small; the offsets are written all the same)
+  int64_t polyfill(GpuContext& ctx, int resolution, int64_t n_polys, const int64_t* poly_part_off,
+                   const int64_t* part_ring_off, const int64_t* ring_off, const double* xy, int64_t* out_cells_dev,
+                   int64_t capacity, int64_t* offsets_dev, void* stream = nullptr) const {
+    const int r = getResolution(resolution);
+    int64_t total = 0;
+    const int32_t st = mgpu_grid_polyfill(ctx.get(), code(), r, n_polys, poly_part_off, part_ring_off, ring_off, xy,
+                                          out_cells_dev, capacity, offsets_dev, &total, stream);
+    check(st, total);
+    return total;
+  }
+
   virtual std::string format(int64_t id) const = 0;
   virtual int64_t parse(const std::string& id) const = 0;
 

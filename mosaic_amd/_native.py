@@ -50,6 +50,7 @@ EXPORTS = (
     "mgpu_cell_agg_size", "mgpu_cell_agg_fetch", "mgpu_cell_agg_clear", "mgpu_cell_agg_destroy",
     "mgpu_cells_to_centers", "mgpu_cells_to_boundaries", "mgpu_cells_boundary_wkb", "mgpu_cells_area",
     "mgpu_test_cell_geometry_host",
+    "mgpu_grid_polyfill", "mgpu_test_grid_polyfill_last", "mgpu_test_grid_polyfill_host",
 )
 MGPU_GEOM_WKB = 0
 MGPU_GEOM_WKT = 1
@@ -211,6 +212,9 @@ def lib():
         "mgpu_cells_boundary_wkb": (I32, [P, I32, P, P, I64, I64, P, I64, P, ctypes.POINTER(I64), P, P]),
         "mgpu_cells_area": (I32, [P, I32, P, P, I64, I64, P, P, P]),
         "mgpu_test_cell_geometry_host": (I32, [I32, P, I64, P, P, P, P]),
+        "mgpu_grid_polyfill": (I32, [P, I32, I32, I64, P, P, P, P, P, I64, P, ctypes.POINTER(I64), P]),
+        "mgpu_test_grid_polyfill_last": (I32, [P]),
+        "mgpu_test_grid_polyfill_host": (I32, [I32, I32, I64, P, P, P, P, P, I64, P, ctypes.POINTER(I64)]),
         "mgpu_ring_join": (I32, [P, I32, I32, I32, I32, P, P, I64, P, P, I64, I64, I32, ctypes.c_double, I64,
                                  ctypes.POINTER(I64), P, P, P, P]),
         "mgpu_ring_join_ex": (I32, [P, I32, I32, I32, I32, P, P, I64, P, P, I64, I64, I32, ctypes.c_double, I32,

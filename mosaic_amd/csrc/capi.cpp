@@ -337,6 +337,9 @@ int32_t mgpu_ctx_set_option(mgpu_ctx* ctx, const char* key, int64_t v) {
   } else if (k == "kring_batch") {
     if (v < 0 || v > 2147483647LL) return bad();
     o.kring_batch = v;
+  } else if (k == "polyfill_slab") {
+    if (v < 256 || v > ((int64_t)1 << 28)) return bad();
+    o.polyfill_slab = v;
   } else if (k == "spin_us") {
     if (v < 0 || v > 10000000) return bad();
     o.spin_us = v;
@@ -364,7 +367,7 @@ int32_t mgpu_ctx_get_option(const mgpu_ctx* ctx, const char* key, int64_t* v) {
       {"bin_keys", o.bin_keys},     {"spin_us", o.spin_us},   {"ring_batch", o.ring_batch},       {"raster", o.raster},     {"raster_bng", o.raster_bng},
       {"bng_split", o.bng_split},   {"count_lds_slots", o.count_lds_slots}, {"count_groups", o.count_groups},
       {"kring_batch", o.kring_batch}, {"cellagg_groups", o.cellagg_groups}, {"cellagg_lds", o.cellagg_lds}, {"cellagg_bin_min", o.cellagg_bin_min},
-      {"raster_sub", o.raster_sub}, {"raster_milli", o.raster_milli}};
+      {"raster_sub", o.raster_sub}, {"raster_milli", o.raster_milli}, {"polyfill_slab", o.polyfill_slab}};
   for (const auto& kv : all)
     if (strcmp(kv.first, key) == 0) {
       *v = kv.second;

@@ -219,6 +219,61 @@ def grid_cellkloop(cells, k, index_system, ctx=None, stream=None):
     return grid_cellkring(cells, k, index_system, loop_only=True, ctx=ctx, stream=stream)
 
 
+_POLYFILL_FIRST_CAPACITY = 1 << 24  # cells (128 MiB): beyond it the reported total sizes the second call
+
+
+def _polyfill_capacity(polygons, index_system, res):
+    """A first output capacity for grid_polyfill: the rings' areas over the index system's
+    cell area, so that the usual set fits at the first call (a short buffer costs a second
+    pass); at most _POLYFILL_FIRST_CAPACITY -- a larger set is sized by the total the first call
+    reports, as grid_cellkring's buffer is."""
+    xy, ro = polygons.xy, polygons.ring_off
+    if len(xy) < 2 or len(ro) < 2:
+        return 1024
+    cross = xy[:-1, 0] * xy[1:, 1] - xy[1:, 0] * xy[:-1, 1]
+    csum = np.concatenate([[0.0], np.cumsum(cross)])
+    # (ring r's edges are the cross products ro[r] .. ro[r + 1] - 2: the one joining two rings is left out)
+    last = np.maximum(ro[1:] - 1, ro[:-1])
+    area = 0.5 * np.abs(csum[last] - csum[ro[:-1]])
+    cells = float(np.sum(area / index_system.cell_area_estimate(res, xy[np.minimum(ro[:-1], len(xy) - 1), 1])))
+    if not np.isfinite(cells):
+        cells = 0.0
+    return int(min(max(1.25 * cells + 64 * len(polygons), 1024), _POLYFILL_FIRST_CAPACITY))
+
+
+def grid_polyfill(polygons, resolution, index_system=None, ctx=None, stream=None):
+    """grid_polyfill(geometry, resolution) (expressions/index/Polyfill.scala -> IndexSystem.polyfill)
+    over a polygon set (``Polygons``), on the GPU (H3, BNG): for each polygon the cells whose
+    centre lies in its interior.  Returns (cells int64 device tensor, offsets int64 device
+    tensor of n + 1): polygon p's cells are cells[offsets[p]:offsets[p + 1]], in the order of
+    the lattice laid over its bounding box (deterministic; not the reference's hash-set order),
+    no cell twice.  The full set: the reference's flood fill / BFS can miss a matching cell that
+    no chain of matching neighbours joins to a seed."""
+    import ctypes
+    import torch
+    from .context import default_context
+    from .index_system import H3IndexSystem
+    index_system = index_system or H3IndexSystem()
+    res = index_system.get_resolution(resolution)
+    ctx = ctx or default_context()
+    dev = ctx.device
+    n = len(polygons)
+    off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    tot = ctypes.c_int64()
+    s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    cap = _polyfill_capacity(polygons, index_system, res)  # grown to the reported size when the set needs more
+    while True:
+        out = torch.empty(cap, dtype=torch.int64, device=dev)
+        st = N.lib().mgpu_grid_polyfill(ctx.handle, index_system.code, res, n, polygons.poly_part_off.ctypes.data,
+                                        polygons.part_ring_off.ctypes.data, polygons.ring_off.ctypes.data,
+                                        polygons.xy.ctypes.data, out.data_ptr(), cap, off.data_ptr(), ctypes.byref(tot), s)
+        if st != N.MGPU_E_CAPACITY or tot.value <= cap:
+            break
+        cap = tot.value
+    N.check(st, required=tot.value)
+    return out[:tot.value], off
+
+
 def grid_boundaryaswkb(cells, index_system, valid=None, valid_offset=0, ctx=None, stream=None):
     """grid_boundaryaswkb (IndexGeometry.scala:65-75 -> IndexSystem.indexToGeometry, as WKB)
     over a device int64 column, on the GPU (H3, BNG).  Returns (bytes uint8 tensor, offsets

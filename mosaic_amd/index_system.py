@@ -209,6 +209,19 @@ class IndexSystem:
                                         None if ov is None else ov.data_ptr(), s))
         return a[:n] if ov is None else (a[:n], ov[:(n + 7) // 8])
 
+    def polyfill(self, geometry, resolution, ctx=None, stream=None):
+        """IndexSystem.polyfill(geometry, resolution, geometryAPI): Seq[Long] (IndexSystem.scala:166)
+        on the device (mgpu_grid_polyfill): the cells whose centre lies in the geometry.  One
+        geometry -- a list of parts, each a list of closed rings [(x, y), ...], the shell first --
+        gives a Python list of ids; a ``Polygons`` set gives functions.grid_polyfill's (cells,
+        offsets) device tensors."""
+        from .chips import Polygons
+        from .functions import grid_polyfill
+        if isinstance(geometry, Polygons):
+            return grid_polyfill(geometry, resolution, self, ctx=ctx, stream=stream)
+        cells, _ = grid_polyfill(Polygons.from_lists([(0, geometry)]), resolution, self, ctx=ctx, stream=stream)
+        return [int(v) for v in cells.cpu().tolist()]
+
     def _one_cell(self, index):
         import torch
         from .context import default_context
@@ -280,6 +293,13 @@ class H3IndexSystem(IndexSystem):
             raise IllegalStateException(N.MGPU_E_RESOLUTION, "H3 resolution has to be between 0 and 15; found %d" % r)
         return r
 
+    def cell_area_estimate(self, resolution, lat):
+        """A lower estimate of a cell's area in square degrees at latitude(s) ``lat``, for sizing
+        buffers (grid_polyfill): H3's mean hexagon area is 4,250,547 km^2 / 7^res, its smallest
+        cells (around the pentagons) about half of that; a degree is 111.32 km."""
+        km2 = 0.5 * 4250546.848 / 7.0 ** resolution
+        return km2 / (111.32 ** 2 * np.cos(np.radians(np.clip(lat, -89.0, 89.0))))
+
     def format(self, cell_id):
         """H3 string form (the 15-hex-digit address)."""
         return "%x" % int(cell_id)
@@ -313,6 +333,16 @@ class BNGIndexSystem(IndexSystem):
         if isinstance(res, str) and res in self.resolution_map:
             return self.resolution_map[res]
         raise IllegalStateException(N.MGPU_E_RESOLUTION, "BNG resolution not supported; found %s" % (res,))
+
+    def edge_size(self, resolution):
+        """BNGIndexSystem.getEdgeSize (BNGIndexSystem.scala:163-170): metres; a quadrant
+        resolution (negative) has half the edge of the grid above it."""
+        r = self.get_resolution(resolution)
+        return 10 ** (6 - r) if r > 0 else 5 * 10 ** (6 + r)
+
+    def cell_area_estimate(self, resolution, lat=None):
+        """A cell's area in square metres, for sizing buffers (grid_polyfill)."""
+        return float(self.edge_size(resolution)) ** 2
 
     def get_resolution_str(self, resolution):
         for k, v in self.resolution_map.items():
