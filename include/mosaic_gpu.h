@@ -142,6 +142,14 @@ int32_t mgpu_ctx_destroy(mgpu_ctx* ctx);
  *   "polyfill_slab"   mgpu_grid_polyfill processes its lattice samples in slabs of at most this
  *                     many (default 2^24, 256..2^28), whose matches wait in context scratch for
  *                     the gather; a slab boundary does not change the output
+ *   "geomring_slab"   mgpu_geometry_kring expands the border cells of its geometries in slabs of at
+ *                     most this many (default 2^16, 1..2^24; and at most what keeps a slab's ring
+ *                     lists within 2^24 ids each), whose lists wait in context scratch; a slab
+ *                     boundary, also one inside a geometry, does not change the output
+ *   "geomring_lds_slots"
+ *                     0 (default): a geometry's LDS set has up to 16384 slots (128 KiB); >= 64: up
+ *                     to the largest power of two not above the value, capped at the default (a
+ *                     test hook: a small value sends geometries down the HBM path)
  *   "raster", "raster_bng", "raster_sub", "raster_milli"
  *                     the chip-table builder of mgpu_chips_upload on this context
  *                     (mgpu_build_opts below)
@@ -245,6 +253,34 @@ int32_t mgpu_bng_format_device(mgpu_ctx* ctx, const int64_t* cells, int64_t n, c
 int32_t mgpu_grid_kring(mgpu_ctx* ctx, int32_t index_system, const int64_t* cells, int64_t n, int32_t k,
                         int32_t loop_only, int64_t* out_cells, int64_t capacity, int64_t* out_offsets,
                         int64_t* out_total, void* stream);
+
+/* Mosaic.geometryKRing / geometryKLoop (core/Mosaic.scala:123-156, getCellSets :226-238) over a
+ * batch of geometries given as chip rows -- grid_geometrykring / grid_geometrykloop and their
+ * explode forms (expressions/index/GeometryKRing.scala, GeometryKLoop.scala).  Geometry g owns the
+ * rows [row_off[g], row_off[g + 1]) of `cell` / `is_core` (the tessellator's index_id and is_core,
+ * keep_core_geometries = false).  With core = its rows with is_core != 0 and border the others, as
+ * sets of cell ids,
+ *   loop_only = 0:  core  u  U_{b in border} kRing(b, k)                                  0 <= k <= 1024
+ *   loop_only = 1:  U_{b in border} kLoop(b, k)  -  (core  u  U_{b in border} kRing(b, k - 1))   1 <= k <= 1024
+ * where kRing / kLoop are mgpu_grid_kring's (H3: the pentagon fallbacks; BNG: invalid cells dropped,
+ * quadrant resolutions).  The definition is computed as it stands: every border cell's lists are
+ * expanded and the sets formed, no metric shortcut.
+ * Output: geometry g's cells are out_cells[out_offsets[g] .. out_offsets[g + 1]), every cell once,
+ * ASCENDING by id (the reference returns an unordered Set; ascending is this library's documented
+ * order: two runs, and the host twin, give the same bytes).  A geometry without rows gives an empty
+ * list, and so does, with loop_only, one with core rows only.  *out_total = the entries needed,
+ * MGPU_E_CAPACITY when above `capacity` (out_offsets is still written in full; the entries that fit
+ * are written); out_cells = NULL with capacity 0 asks for the size.
+ * MGPU_E_INVALID_ARG: k outside its range (the reference's kRing(b, -1) for a loop of k = 0 has no
+ * meaning), a border row that is not a cell id of the index system (mgpu_grid_kring's verdict), a
+ * core row outside [0, 2^62) (no cell id of either system), row_off decreasing or negative.
+ * MGPU_E_UNSUPPORTED: one geometry with 2^31 or more ring ids within a slab that did not fit its
+ * LDS set (lower "geomring_slab").
+ * All pointers are device pointers; the call synchronises `stream` (several times: it reads the
+ * geometries' sizes and each slab's verdicts back).  Options "geomring_slab", "geomring_lds_slots". */
+int32_t mgpu_geometry_kring(mgpu_ctx* ctx, int32_t index_system, int64_t n_geoms, const int64_t* row_off, const int64_t* cell,
+                            const uint8_t* is_core, int32_t k, int32_t loop_only, int64_t* out_cells, int64_t capacity,
+                            int64_t* out_offsets, int64_t* out_total, void* stream);
 
 /* Cell id -> geometry over a device column of cells: what grid_boundaryaswkb /
  * grid_boundary (expressions/index/IndexGeometry.scala:65-75) and grid_cellarea
@@ -749,6 +785,18 @@ int32_t mgpu_test_grid_polyfill_host(int32_t index_system, int32_t res, int64_t 
  * failures over all attempts, attempts (1 = the first spacing held), device microseconds of the
  * last attempt's launches between two events on its stream (the host twin: 0), 0, 0, 0. */
 int32_t mgpu_test_grid_polyfill_last(int64_t* out8);
+/* TEST ONLY: mgpu_geometry_kring's host twin -- the same contract on host arrays (no GPU), from
+ * the ring code the kernels run compiled for the host (h3_ring.h, bng_core.h); the same bytes. */
+int32_t mgpu_test_geometry_kring_host(int32_t index_system, int64_t n_geoms, const int64_t* row_off, const int64_t* cell,
+                                      const uint8_t* is_core, int32_t k, int32_t loop_only, int64_t* out_cells,
+                                      int64_t capacity, int64_t* out_offsets, int64_t* out_total);
+/* TEST ONLY (and tools/geomring_time.py): figures of the last mgpu_geometry_kring or
+ * mgpu_test_geometry_kring_host call made on the CALLING THREAD (thread-local, overwritten by
+ * either entry; zeros before the first call): out8 = geometries finished on the LDS path,
+ * geometries finished on the HBM path, slabs run, border cells, ids generated (the lists' ids plus
+ * one per row), ids returned, microseconds between the first and last launch on the stream (host
+ * waits in between included; the twin: 0), border cells that took an H3 pentagon fallback. */
+int32_t mgpu_test_geometry_kring_last(int64_t* out8);
 /* TEST ONLY: an H3 cell's geometry as a core chip of it carries it (indexToGeometry,
  * H3IndexSystem.scala:103-112: the polar caps of makePoleGeometry, antimeridian cells
  * cut) as WKB into out[cap]; *out_len = its size (MGPU_E_CAPACITY when it exceeds cap). */

@@ -174,6 +174,21 @@ class IndexSystem {
     return total;
   }
 
+  // Mosaic.geometryKRing / geometryKLoop over a batch of geometries given as chip rows (core/Mosaic.scala:
+  // 123-156; mgpu_geometry_kring): geometry g owns the rows [row_off_dev[g], row_off_dev[g + 1]) of cell_dev /
+  // is_core_dev; its cells, once each and ascending, go to out_cells_dev[capacity], its range to
+  // offsets_dev[g .. g + 1] (device).  loop_only: the k-loop (k >= 1) instead of the k-ring (k >= 0).  Returns the
+  // cells needed (CapacityError.required when `capacity` is too small; the offsets are written all the same)
+  int64_t geometry_k_ring(GpuContext& ctx, int64_t n_geoms, const int64_t* row_off_dev, const int64_t* cell_dev,
+                          const uint8_t* is_core_dev, int k, bool loop_only, int64_t* out_cells_dev, int64_t capacity,
+                          int64_t* offsets_dev, void* stream = nullptr) const {
+    int64_t total = 0;
+    const int32_t st = mgpu_geometry_kring(ctx.get(), code(), n_geoms, row_off_dev, cell_dev, is_core_dev, k, loop_only ? 1 : 0,
+                                           out_cells_dev, capacity, offsets_dev, &total, stream);
+    check(st, total);
+    return total;
+  }
+
   virtual std::string format(int64_t id) const = 0;
   virtual int64_t parse(const std::string& id) const = 0;
 

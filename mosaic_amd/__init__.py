@@ -11,16 +11,16 @@ from ._native import (CapacityError, IllegalArgumentException, IllegalStateExcep
                       EXPORTS, LIB_PATH)
 from .chips import ChipTable, DeviceChips, Polygons, tessellate
 from .context import GpuContext, MosaicContext, default_context
-from .functions import (AsyncJoin, CellAggregate, CellCounts, CountResult, GeometryColumn, InternalGeometryColumn, JoinResult, LookupResult, grid_boundary, grid_boundaryaswkb, grid_cellarea, grid_cellcount, grid_cellkloop, grid_cellkring, grid_longlatascellid, grid_pointascellid, grid_polyfill,
+from .functions import (AsyncJoin, CellAggregate, CellCounts, CountResult, GeometryColumn, GeometryRings, InternalGeometryColumn, JoinResult, LookupResult, grid_boundary, grid_boundaryaswkb, grid_cellarea, grid_cellcount, grid_cellkloop, grid_cellkring, grid_geometrykloop, grid_geometrykloopexplode, grid_geometrykring, grid_geometrykringexplode, grid_longlatascellid, grid_pointascellid, grid_polyfill,
                         grid_ring_join, grid_ring_join_final, grid_tessellateexplode, pip_join, pip_join_async, pip_join_count, pip_join_lookup, points_from_geometry, st_contains)
 from .index_system import BNGIndexSystem, H3IndexSystem, IndexSystem, get_index_system
 
 __version__ = "0.1.0"
 
 __all__ = [
-    "AsyncJoin", "BNGIndexSystem", "CapacityError", "CellAggregate", "CellCounts", "ChipTable", "CountResult", "DeviceChips", "EXPORTS", "GeometryColumn", "GpuContext", "InternalGeometryColumn", "H3IndexSystem",
+    "AsyncJoin", "BNGIndexSystem", "CapacityError", "CellAggregate", "CellCounts", "ChipTable", "CountResult", "DeviceChips", "EXPORTS", "GeometryColumn", "GeometryRings", "GpuContext", "InternalGeometryColumn", "H3IndexSystem",
     "IllegalArgumentException", "IllegalStateException", "IndexSystem", "JoinResult", "LIB_PATH", "LookupResult",
     "MosaicContext", "MosaicGpuError", "Polygons", "default_context", "get_index_system", "grid_boundary", "grid_boundaryaswkb", "grid_cellarea", "grid_cellcount", "grid_cellkloop",
-    "grid_cellkring", "grid_longlatascellid", "grid_polyfill",
+    "grid_cellkring", "grid_geometrykloop", "grid_geometrykloopexplode", "grid_geometrykring", "grid_geometrykringexplode", "grid_longlatascellid", "grid_polyfill",
     "grid_pointascellid", "grid_ring_join", "grid_ring_join_final", "grid_tessellateexplode", "pip_join", "pip_join_async", "pip_join_count", "pip_join_lookup", "points_from_geometry", "st_contains", "tessellate",
 ]

@@ -51,6 +51,7 @@ EXPORTS = (
     "mgpu_cells_to_centers", "mgpu_cells_to_boundaries", "mgpu_cells_boundary_wkb", "mgpu_cells_area",
     "mgpu_test_cell_geometry_host",
     "mgpu_grid_polyfill", "mgpu_test_grid_polyfill_last", "mgpu_test_grid_polyfill_host",
+    "mgpu_geometry_kring", "mgpu_test_geometry_kring_host", "mgpu_test_geometry_kring_last",
 )
 MGPU_GEOM_WKB = 0
 MGPU_GEOM_WKT = 1
@@ -215,6 +216,9 @@ def lib():
         "mgpu_grid_polyfill": (I32, [P, I32, I32, I64, P, P, P, P, P, I64, P, ctypes.POINTER(I64), P]),
         "mgpu_test_grid_polyfill_last": (I32, [P]),
         "mgpu_test_grid_polyfill_host": (I32, [I32, I32, I64, P, P, P, P, P, I64, P, ctypes.POINTER(I64)]),
+        "mgpu_geometry_kring": (I32, [P, I32, I64, P, P, P, I32, I32, P, I64, P, ctypes.POINTER(I64), P]),
+        "mgpu_test_geometry_kring_host": (I32, [I32, I64, P, P, P, I32, I32, P, I64, P, ctypes.POINTER(I64)]),
+        "mgpu_test_geometry_kring_last": (I32, [P]),
         "mgpu_ring_join": (I32, [P, I32, I32, I32, I32, P, P, I64, P, P, I64, I64, I32, ctypes.c_double, I64,
                                  ctypes.POINTER(I64), P, P, P, P]),
         "mgpu_ring_join_ex": (I32, [P, I32, I32, I32, I32, P, P, I64, P, P, I64, I64, I32, ctypes.c_double, I32,

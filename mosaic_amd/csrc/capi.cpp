@@ -340,6 +340,12 @@ int32_t mgpu_ctx_set_option(mgpu_ctx* ctx, const char* key, int64_t v) {
   } else if (k == "polyfill_slab") {
     if (v < 256 || v > ((int64_t)1 << 28)) return bad();
     o.polyfill_slab = v;
+  } else if (k == "geomring_slab") {
+    if (v < 1 || v > ((int64_t)1 << 24)) return bad();
+    o.geomring_slab = v;
+  } else if (k == "geomring_lds_slots") {
+    if (v != 0 && v < 64) return bad();  // (geom_ring.h kLdsSlotsMin; above kLdsSlots: capped)
+    o.geomring_lds_slots = v;
   } else if (k == "spin_us") {
     if (v < 0 || v > 10000000) return bad();
     o.spin_us = v;
@@ -367,7 +373,8 @@ int32_t mgpu_ctx_get_option(const mgpu_ctx* ctx, const char* key, int64_t* v) {
       {"bin_keys", o.bin_keys},     {"spin_us", o.spin_us},   {"ring_batch", o.ring_batch},       {"raster", o.raster},     {"raster_bng", o.raster_bng},
       {"bng_split", o.bng_split},   {"count_lds_slots", o.count_lds_slots}, {"count_groups", o.count_groups},
       {"kring_batch", o.kring_batch}, {"cellagg_groups", o.cellagg_groups}, {"cellagg_lds", o.cellagg_lds}, {"cellagg_bin_min", o.cellagg_bin_min},
-      {"raster_sub", o.raster_sub}, {"raster_milli", o.raster_milli}, {"polyfill_slab", o.polyfill_slab}};
+      {"raster_sub", o.raster_sub}, {"raster_milli", o.raster_milli}, {"polyfill_slab", o.polyfill_slab},
+      {"geomring_slab", o.geomring_slab}, {"geomring_lds_slots", o.geomring_lds_slots}};
   for (const auto& kv : all)
     if (strcmp(kv.first, key) == 0) {
       *v = kv.second;

@@ -27,6 +27,8 @@ struct mgpu_options {
   int64_t cellagg_lds = 1;                // ... behind a per-workgroup LDS hash table (0: every addition goes to the global table)
   int64_t cellagg_bin_min = (int64_t)1 << 22;  // ... columns of at least this many cells are binned by hash first when they hold many distinct cells (0: never)
   int64_t polyfill_slab = (int64_t)1 << 24;  // mgpu_grid_polyfill: lattice samples whose matches are held in scratch at a time
+  int64_t geomring_slab = (int64_t)1 << 16;  // mgpu_geometry_kring: border cells whose ring lists are held in scratch at a time
+  int64_t geomring_lds_slots = 0;         // ... slots of a geometry's LDS set (0: the default and maximum, geom_ring.h kLdsSlots; a test hook)
   int64_t bng_split = 0;                  // BNG dense tables: the split pipeline, the grid entry as the code (A/B r6: C4 2.43 vs 2.17 ms fused -- off)
   // the chip-table builder of mgpu_chips_upload on this context (mgpu_build_opts)
   int64_t raster = 1, raster_bng = 0, raster_sub = 16, raster_milli = 250;

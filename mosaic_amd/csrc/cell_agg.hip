@@ -734,6 +734,32 @@ int32_t agg_size(mgpu_ctx* ctx, const mgpu_cell_agg* a, hipStream_t s, int64_t* 
 
 }  // namespace
 
+namespace mgpu {
+
+// kernels.h: the radix sort above for another unit (geom_ring.hip's HBM path)
+int64_t sort_pairs_hist_words(int64_t n) { return ((n + kSortTile - 1) / kSortTile + 1) * 256; }
+
+hipError_t launch_sort_pairs(unsigned long long** k0, unsigned long long** v0, unsigned long long** k1,
+                             unsigned long long** v1, int64_t n, unsigned long long differ, uint32_t* hist, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  const int64_t tiles = (n + kSortTile - 1) / kSortTile;
+  uint32_t* tot = hist + tiles * 256;
+  const dim3 sgrid((unsigned)((tiles + kSortWaves - 1) / kSortWaves));
+  for (int d = 0; d < 8; d++) {
+    if (((differ >> (8 * d)) & 0xFFu) == 0) continue;  // this digit is equal in all keys
+    hipLaunchKernelGGL(sort_hist_kernel, sgrid, dim3(64 * kSortWaves), 0, s, *k0, n, tiles, d, hist);
+    hipLaunchKernelGGL(scan_rows_kernel, dim3(256), dim3(256), 0, s, hist, tiles, tot);
+    hipLaunchKernelGGL(scan_tot_kernel, dim3(1), dim3(1024), 0, s, tot, 256);
+    hipLaunchKernelGGL(sort_scatter_kernel, sgrid, dim3(64 * kSortWaves), 0, s, *k0, *v0, n, tiles, d, hist, tot, *k1, *v1);
+    if (hipError_t e = hipGetLastError()) return e;
+    std::swap(*k0, *k1);
+    std::swap(*v0, *v1);
+  }
+  return hipSuccess;
+}
+
+}  // namespace mgpu
+
 extern "C" {
 
 int32_t mgpu_cell_agg_create(mgpu_ctx* ctx, int32_t index_system, int32_t res, int32_t with_sum, int64_t initial_cells,

@@ -288,6 +288,13 @@ hipError_t launch_kring_fallback(const int64_t* cells, const uint32_t* fb_idx, i
                                  hipStream_t s);
 hipError_t launch_kring_write(int is, const int64_t* cells, int64_t n, int k, int loop_only, const int64_t* mc,
                               int64_t* chunk, int64_t* offsets, int64_t* out, int64_t capacity, hipStream_t s);
+// cell_agg.hip's LSD radix sort (8-bit digits, stable, unsigned with the top bit flipped) of n <
+// 2^31 (key, value) records: *k0 / *v0 in, *k1 / *v1 the other side; on return *k0 / *v0 hold the
+// sorted records (the sides are swapped pass by pass).  A digit whose byte of `differ` is 0 is
+// skipped (equal in all keys).  hist: sort_pairs_hist_words(n) u32 of scratch.
+int64_t sort_pairs_hist_words(int64_t n);
+hipError_t launch_sort_pairs(unsigned long long** k0, unsigned long long** v0, unsigned long long** k1,
+                             unsigned long long** v1, int64_t n, unsigned long long differ, uint32_t* hist, hipStream_t s);
 // counters[2] += chip rows outside [0, n_chips) (their out is -2)
 hipError_t launch_st_contains(const ChipTableView& t, const int64_t* row, const double* x, const double* y, int64_t n,
                               int8_t* out, unsigned long long* counters, hipStream_t s);

@@ -274,6 +274,131 @@ def grid_polyfill(polygons, resolution, index_system=None, ctx=None, stream=None
     return out[:tot.value], off
 
 
+class GeometryRings:
+    """grid_geometrykring / grid_geometrykloop of a batch: ``ids`` (int32 numpy array: the
+    geometries' polygon ids, ascending, as ``DeviceChips.polygons()`` orders them; 0 .. n - 1 for
+    geometries without ids), ``cells`` (int64 device tensor) and ``offsets`` (int64 device tensor of
+    len(ids) + 1): geometry ids[g]'s cells are cells[offsets[g]:offsets[g + 1]], ascending."""
+
+    def __init__(self, ids, cells, offsets):
+        self.ids, self.cells, self.offsets = ids, cells, offsets
+
+    def __len__(self):
+        return len(self.ids)
+
+    def lists(self):
+        """The lists on the host: one int64 numpy array per geometry."""
+        c, o = self.cells.cpu().numpy(), self.offsets.cpu().numpy()
+        return [c[o[g]:o[g + 1]] for g in range(len(self.ids))]
+
+    def explode(self):
+        """(row, cell) device columns, one row per (geometry, cell): row g repeated for each of
+        its cells -- the explode forms' output."""
+        import torch
+        n = self.offsets[1:] - self.offsets[:-1]
+        row = torch.repeat_interleave(torch.arange(len(self.ids), dtype=torch.int64, device=self.cells.device), n)
+        return row, self.cells
+
+
+def _geometry_rows(geoms, index_system, resolution, ctx, stream):
+    """(ids, row_off, cell, is_core, n_rows) of grid_geometrykring's ``geoms``, the three columns on the device."""
+    import torch
+    from .chips import Polygons
+    dev = ctx.device
+    if isinstance(geoms, Polygons):
+        if resolution is None:
+            raise N.IllegalArgumentException(N.MGPU_E_INVALID_ARG, "a Polygons set needs a resolution")
+        geoms = tessellate(geoms, index_system, resolution, keep_core_geometries=False)  # (as Mosaic.getCellSets)
+    if isinstance(geoms, ChipTable):
+        if geoms.index_system != index_system.code:
+            raise N.IllegalArgumentException(N.MGPU_E_INVALID_ARG, "the chip table belongs to another index system")
+        order = np.argsort(geoms.polygon_id, kind="stable")
+        pid = geoms.polygon_id[order]
+        ids = np.unique(pid).astype(np.int32)
+        row_off = np.append(np.searchsorted(pid, ids, side="left"), len(pid)).astype(np.int64)
+        return (ids, torch.from_numpy(row_off).to(dev), torch.from_numpy(geoms.cell[order]).to(dev),
+                torch.from_numpy(geoms.is_core[order]).to(dev), len(pid))
+    if isinstance(geoms, (tuple, list)) and len(geoms) == 3:
+        row_off, cell, is_core = geoms
+        if (row_off.dtype != torch.int64 or cell.dtype != torch.int64 or is_core.dtype not in (torch.uint8, torch.bool)
+                or not (row_off.is_cuda and cell.is_cuda and is_core.is_cuda) or row_off.numel() < 1
+                or cell.numel() != is_core.numel()):
+            raise N.IllegalArgumentException(N.MGPU_E_INVALID_ARG, "(row_off int64, cell int64, is_core uint8) device tensors expected")
+        is_core = is_core.contiguous()
+        if is_core.dtype == torch.bool:
+            is_core = is_core.view(torch.uint8)
+        n = row_off.numel() - 1
+        return np.arange(n, dtype=np.int32), row_off.contiguous(), cell.contiguous(), is_core, cell.numel()
+    if isinstance(geoms, (tuple, list)) and len(geoms) == 2:
+        if resolution is None:
+            raise N.IllegalArgumentException(N.MGPU_E_INVALID_ARG, "point columns need a resolution")
+        x, y = geoms
+        cell = grid_longlatascellid(x, y, resolution, index_system, ctx=ctx, stream=stream)  # (Mosaic.pointChip: one border chip)
+        n = cell.numel()
+        return (np.arange(n, dtype=np.int32), torch.arange(n + 1, dtype=torch.int64, device=dev), cell,
+                torch.zeros(n, dtype=torch.uint8, device=dev), n)
+    raise N.IllegalArgumentException(N.MGPU_E_INVALID_ARG, "geoms: a ChipTable, a Polygons set, (row_off, cell, is_core) or (x, y)")
+
+
+def _geometry_rings(geoms, k, index_system, resolution, loop_only, ctx, stream):
+    import ctypes
+    import torch
+    from .context import default_context
+    if ctx is None:
+        t = geoms[0] if isinstance(geoms, (tuple, list)) else None
+        ctx = default_context(t.device) if t is not None and getattr(t, "is_cuda", False) else default_context()
+    dev = ctx.device
+    k = int(k)
+    s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    ids, row_off, cell, is_core, n_rows = _geometry_rows(geoms, index_system, resolution, ctx, s if stream is not None else None)
+    n = len(ids)
+    off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    tot = ctypes.c_int64()
+    # a first capacity: per row its own cell and the cells a border row adds along a border line,
+    # per geometry one whole list; grown once to the reported total when the sets need more
+    one = 8 * max(k, 1) if loop_only else 1 + 4 * k * (k + 1)
+    cap = int(min(n_rows * one, n_rows * (2 * k + 2) + n * one) + 1024)
+    while True:
+        out = torch.empty(cap, dtype=torch.int64, device=dev)
+        st = N.lib().mgpu_geometry_kring(ctx.handle, index_system.code, n, row_off.data_ptr(), cell.data_ptr(),
+                                         is_core.data_ptr(), k, 1 if loop_only else 0, out.data_ptr(), cap, off.data_ptr(),
+                                         ctypes.byref(tot), s)
+        if st != N.MGPU_E_CAPACITY or tot.value <= cap:
+            break
+        cap = tot.value
+    N.check(st, required=tot.value)
+    return GeometryRings(ids, out[:tot.value], off)
+
+
+def grid_geometrykring(geoms, k, index_system, resolution=None, ctx=None, stream=None):
+    """grid_geometrykring(geometry, resolution, k) (expressions/index/GeometryKRing.scala ->
+    Mosaic.geometryKRing, core/Mosaic.scala:123-137) over a batch, on the GPU (H3, BNG): per
+    geometry, its core cells and the k-rings of its border cells, every cell once, ascending.
+    ``geoms``: a ``ChipTable`` (rows grouped by polygon id), a ``(row_off, cell, is_core)`` triple
+    of device tensors (geometry g owns rows row_off[g]:row_off[g + 1]), a ``Polygons`` set with
+    ``resolution`` (tessellated without core geometries, as the reference does), or an ``(x, y)``
+    pair of float64 device columns with ``resolution`` (each point one border chip).  Returns a
+    ``GeometryRings``.  k in [0, 1024]."""
+    return _geometry_rings(geoms, k, index_system, resolution, False, ctx, stream)
+
+
+def grid_geometrykloop(geoms, k, index_system, resolution=None, ctx=None, stream=None):
+    """grid_geometrykloop (GeometryKLoop.scala -> Mosaic.geometryKLoop, core/Mosaic.scala:139-156):
+    the k-loops of the border cells without the core cells and the border cells' (k - 1)-rings;
+    arguments and result as grid_geometrykring.  k in [1, 1024]."""
+    return _geometry_rings(geoms, k, index_system, resolution, True, ctx, stream)
+
+
+def grid_geometrykringexplode(geoms, k, index_system, resolution=None, ctx=None, stream=None):
+    """grid_geometrykringexplode: grid_geometrykring as (row, cell) device columns, one row per cell."""
+    return grid_geometrykring(geoms, k, index_system, resolution, ctx, stream).explode()
+
+
+def grid_geometrykloopexplode(geoms, k, index_system, resolution=None, ctx=None, stream=None):
+    """grid_geometrykloopexplode: grid_geometrykloop as (row, cell) device columns, one row per cell."""
+    return grid_geometrykloop(geoms, k, index_system, resolution, ctx, stream).explode()
+
+
 def grid_boundaryaswkb(cells, index_system, valid=None, valid_offset=0, ctx=None, stream=None):
     """grid_boundaryaswkb (IndexGeometry.scala:65-75 -> IndexSystem.indexToGeometry, as WKB)
     over a device int64 column, on the GPU (H3, BNG).  Returns (bytes uint8 tensor, offsets

@@ -222,6 +222,26 @@ class IndexSystem:
         cells, _ = grid_polyfill(Polygons.from_lists([(0, geometry)]), resolution, self, ctx=ctx, stream=stream)
         return [int(v) for v in cells.cpu().tolist()]
 
+    def geometry_k_ring(self, geometry, resolution, k, ctx=None, stream=None):
+        """Mosaic.geometryKRing(geometry, resolution, k, indexSystem, geometryAPI) (core/Mosaic.scala:
+        123-137) for one geometry (parts of closed rings, as ``polyfill`` takes them) on the device
+        (mgpu_geometry_kring, a batch of one): the Python list of its cell ids, ascending."""
+        return self._geometry_k(geometry, resolution, k, False, ctx, stream)
+
+    def geometry_k_loop(self, geometry, resolution, k, ctx=None, stream=None):
+        """Mosaic.geometryKLoop (core/Mosaic.scala:139-156) for one geometry; as geometry_k_ring."""
+        return self._geometry_k(geometry, resolution, k, True, ctx, stream)
+
+    def _geometry_k(self, geometry, resolution, k, loop_only, ctx, stream):
+        from .chips import Polygons
+        from .functions import grid_geometrykloop, grid_geometrykring
+        fn = grid_geometrykloop if loop_only else grid_geometrykring
+        polys = geometry if isinstance(geometry, Polygons) else Polygons.from_lists([(0, geometry)])
+        res = fn(polys, k, self, resolution=resolution, ctx=ctx, stream=stream)
+        if isinstance(geometry, Polygons):
+            return res
+        return [int(v) for v in res.cells.cpu().tolist()]
+
     def _one_cell(self, index):
         import torch
         from .context import default_context
