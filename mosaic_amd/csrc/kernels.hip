@@ -1326,6 +1326,8 @@ __device__ __forceinline__ uint32_t bng_grid_class(const JoinArgs& a, int64_t p,
 // pixel and rank loads, batch g - 1's sub-pixel loads, batch g + 1's coordinates in
 // flight before any wait: 0.806 ms vs 0.765 on C2 at batch 4 (6 waves/SIMD), 0.841 at
 // batch 2; the speculative rank loads add requests and the chain is not the limit.)
+// (Round 10: within a batch the lookups are staged, raster_class_batch below; batch 8 with
+// the staged lookup takes 102 VGPRs, two workgroups per CU, and was not measured.)
 #ifndef MGPU_CFY_BLOCK
 #define MGPU_CFY_BLOCK 512
 #endif
@@ -1337,6 +1339,72 @@ constexpr int kCfyBlock = MGPU_CFY_BLOCK;
 #define MGPU_CFY_WAVES 1  // (8 = at most 64 VGPRs: spills, slower on C2 / C5)
 #endif
 constexpr int kCfyBatch = MGPU_CFY_BATCH;
+
+// raster_class_blk for the N points of a batch at once, on the H3 default table (block
+// table and row bands in LDS, no palette: cfy_staged).  raster_class_blk is an if ladder
+// -- block class, then the pixel's, then its sub-pixel's -- and a load cannot move above
+// the branch that guards it, so N points cost 2 N memory round trips in program order.
+// Here every stage is issued for all N points before any of it is used: a lane that needs
+// no load reads index 0 (such lanes share one line: one request per instruction) and the
+// result is selected afterwards, so a batch costs two round trips, not 2 N.  cl[k] is bit
+// for bit raster_class_blk's answer (kPixEmpty / kPixMixed for ri = kNoPixel /
+// kRasterFull); an invalid point comes with ri = bi = kNoPixel, sub = 0.
+template <int N>
+__device__ __forceinline__ void raster_class_batch(const ChipTableView& t, const uint16_t* blk, const uint32_t* band,
+                                                   const uint32_t (&ri)[N], const uint32_t (&bi)[N],
+                                                   const uint32_t (&sub)[N], uint32_t (&cl)[N]) {
+  const uint32_t s2 = t.raster_sub_n * t.raster_sub_n;
+  uint32_t c[N], bb[N], px[N], q[N];
+  bool pix[N], ref[N];
+#pragma unroll
+  for (int k = 0; k < N; k++) {
+    c[k] = blk[bi[k] != kNoPixel ? bi[k] : 0u];
+    bb[k] = band[sub[k] >> 16];  // (the point's row band, 0 for an invalid point)
+  }
+#pragma unroll
+  for (int k = 0; k < N; k++) {
+    pix[k] = ri[k] < kRasterFull && (bi[k] == kNoPixel || c[k] == kPixMixed);
+    px[k] = t.raster[pix[k] ? ri[k] : 0u];
+  }
+#pragma unroll
+  for (int k = 0; k < N; k++) {
+    ref[k] = pix[k] && px[k] >= 0x8000u && px[k] != kPixMixed;
+    const uint64_t i = ((uint64_t)bb[k] + (px[k] & 0x7FFFu)) * s2 + (sub[k] & 0xFFFFu);
+    q[k] = t.raster_sub[ref[k] ? i : 0ull];
+  }
+#pragma unroll
+  for (int k = 0; k < N; k++)
+    cl[k] = ri[k] >= kRasterFull ? (ri[k] == kRasterFull ? kPixMixed : kPixEmpty) : ref[k] ? q[k] : pix[k] ? px[k] : c[k];
+}
+
+// Whether raster_class_batch answers this table (wave-uniform: tested once per kernel).
+// Index 0 of the four tables is what an idle lane reads: the block table, the bands and
+// the raster have an entry by these counts; raster_sub is there with a second level
+// (raster_sub_n), and the blob gives every array at least one zero-padded 256-byte slot
+// (chip_build.cpp layout_blob), so its index 0 is readable even when no pixel is refined
+// -- no lane selects what it read there.
+__device__ __forceinline__ bool cfy_staged(const ChipTableView& t, uint32_t nblk) {
+  return t.raster_blk && nblk && t.raster_band && t.raster_nband && !t.raster_pal && t.raster_sub && t.raster_sub_n &&
+         t.raster_nx && t.raster_ny;
+}
+
+// run(staged, nulls) with both switches as compile-time constants.  BNG keeps the one
+// general form (no staged lookup; pt_valid tests for the bitmap itself).
+template <int IS, class F>
+__device__ __forceinline__ void cfy_dispatch(bool staged, bool nulls, F& run) {
+  if constexpr (IS == MGPU_H3) {
+    if (staged) {
+      if (nulls) run(std::true_type{}, std::true_type{});
+      else run(std::true_type{}, std::false_type{});
+    } else {
+      if (nulls) run(std::false_type{}, std::true_type{});
+      else run(std::false_type{}, std::false_type{});
+    }
+  } else {
+    run(std::false_type{}, std::true_type{});
+  }
+}
+
 template <int IS>
 __global__ __launch_bounds__(kCfyBlock) __attribute__((amdgpu_waves_per_eu(MGPU_CFY_WAVES))) void classify_wave_kernel(SplitArgs sa, int64_t n_chunks) {
   using Code = typename CodeOf<IS>::T;
@@ -1360,23 +1428,26 @@ __global__ __launch_bounds__(kCfyBlock) __attribute__((amdgpu_waves_per_eu(MGPU_
   const unsigned long long below = (1ull << lane) - 1ull;
   bool any_bad = false;
   const int64_t ch_step = (int64_t)gridDim.x * kW;
-  double bx[kCfyBatch], by[kCfyBatch];
-  auto load_batch = [&](int64_t ch, int b, double* X, double* Y) {
-#pragma unroll
-    for (int k = 0; k < kCfyBatch; k++) {
-      const int64_t p = ch * kChunk + (int64_t)(b + k) * 64 + lane;
-      X[k] = Y[k] = 0.0;
-      if (ch < n_chunks && p < a.n) {
-        X[k] = __builtin_nontemporal_load(&a.x[p]);
-        Y[k] = __builtin_nontemporal_load(&a.y[p]);
-      }
-    }
-  };
-  for (int64_t ch = (int64_t)blockIdx.x * kW + wave; ch < n_chunks; ch += ch_step) {
+  // One chunk.  The three switches are wave-uniform and decided outside the batch loop:
+  // kStaged: raster_class_batch answers the table (cfy_staged); kNulls: the join has a
+  // validity bitmap (else no per-point test); kFull: the chunk lies wholly inside n (every
+  // chunk but the last), so nothing is bounds-tested and the batch's coordinate loads
+  // issue together.  (BNG runs the one general form, <false, true, false>: cfy_dispatch.)
+  auto run_chunk = [&](int64_t ch, auto staged_c, auto nulls_c, auto full_c) {
+    constexpr bool kStaged = decltype(staged_c)::value, kNulls = decltype(nulls_c)::value, kFull = decltype(full_c)::value;
     const int64_t c0 = ch * kChunk;
     uint32_t pairs = 0, nmixed = 0;  // nmixed: wave-uniform
     for (int b = 0; b < kItems; b += kCfyBatch) {
-      load_batch(ch, b, bx, by);
+      double bx[kCfyBatch], by[kCfyBatch];
+#pragma unroll
+      for (int k = 0; k < kCfyBatch; k++) {
+        const int64_t p = c0 + (int64_t)(b + k) * 64 + lane;
+        bx[k] = by[k] = 0.0;
+        if (kFull || p < a.n) {
+          bx[k] = __builtin_nontemporal_load(&a.x[p]);
+          by[k] = __builtin_nontemporal_load(&a.y[p]);
+        }
+      }
       uint32_t ri[kCfyBatch], gix[kCfyBatch], sb[kCfyBatch], bi[kCfyBatch];
 #pragma unroll
       for (int k = 0; k < kCfyBatch; k++) {
@@ -1385,7 +1456,7 @@ __global__ __launch_bounds__(kCfyBlock) __attribute__((amdgpu_waves_per_eu(MGPU_
         sb[k] = 0;
         bi[k] = kNoPixel;
         const int64_t pk = c0 + (int64_t)(b + k) * 64 + lane;
-        if (pk < a.n && pt_valid(a.valid, a.valid_off, pk)) {
+        if ((kFull || pk < a.n) && (!kNulls || pt_valid(a.valid, a.valid_off, pk))) {
           bool ok = true;
           uint32_t g_ = 0, s_ = 0, b_ = kNoPixel;
           if (IS == MGPU_BNG && bng_grid) {
@@ -1405,34 +1476,40 @@ __global__ __launch_bounds__(kCfyBlock) __attribute__((amdgpu_waves_per_eu(MGPU_
 #ifndef MGPU_CFY_ABLATE
 #define MGPU_CFY_ABLATE 0  // profiling only (wrong answers): 1 no lookups, 2 LDS blocks only, 3 no sub-pixels
 #endif
+      if constexpr (kStaged) {
+        raster_class_batch<kCfyBatch>(t, s_blk, s_band, ri, bi, sb, cl);
 #pragma unroll
-      for (int k = 0; k < kCfyBatch; k++) {
+        for (int k = 0; k < kCfyBatch; k++) ge[k] = 0ull;
+      } else {
+#pragma unroll
+        for (int k = 0; k < kCfyBatch; k++) {
 #if MGPU_CFY_ABLATE == 1
-        cl[k] = ri[k] < kRasterFull ? (ri[k] & 1) : kPixEmpty;
+          cl[k] = ri[k] < kRasterFull ? (ri[k] & 1) : kPixEmpty;
 #elif MGPU_CFY_ABLATE == 2
-        cl[k] = ri[k] < kRasterFull && bi[k] != kNoPixel && s_blk[bi[k]] != kPixMixed ? s_blk[bi[k]] : kPixEmpty;
+          cl[k] = ri[k] < kRasterFull && bi[k] != kNoPixel && s_blk[bi[k]] != kPixMixed ? s_blk[bi[k]] : kPixEmpty;
 #elif MGPU_CFY_ABLATE == 3
-        cl[k] = ri[k] < kRasterFull ? (bi[k] != kNoPixel && s_blk[bi[k]] != kPixMixed ? s_blk[bi[k]] : t.raster[ri[k]])
-                                    : kPixEmpty;
+          cl[k] = ri[k] < kRasterFull ? (bi[k] != kNoPixel && s_blk[bi[k]] != kPixMixed ? s_blk[bi[k]] : t.raster[ri[k]])
+                                      : kPixEmpty;
 #elif MGPU_CFY_ABLATE == 4
-        cl[k] = ri[k] < kRasterFull ? t.raster[ri[k]] : kPixEmpty;  // every lane loads its pixel
+          cl[k] = ri[k] < kRasterFull ? t.raster[ri[k]] : kPixEmpty;  // every lane loads its pixel
 #elif MGPU_CFY_ABLATE == 5
-        cl[k] = ri[k] < kRasterFull ? (bi[k] != kNoPixel && s_blk[bi[k]] != kPixMixed ? s_blk[bi[k]] : kPixMixed)
-                                    : kPixEmpty;  // (LDS, then every non-uniform block point mixed: no global loads)
+          cl[k] = ri[k] < kRasterFull ? (bi[k] != kNoPixel && s_blk[bi[k]] != kPixMixed ? s_blk[bi[k]] : kPixMixed)
+                                      : kPixEmpty;  // (LDS, then every non-uniform block point mixed: no global loads)
 #else
-        if (IS == MGPU_BNG && bng_grid)
-          cl[k] = ri[k] == kRasterFull ? kPixMixed : (ri[k] == kNoPixel ? kPixEmpty : ri[k]);
-        else
-          cl[k] = ri[k] < kRasterFull ? raster_class_blk(t, s_blk, ri[k], bi[k], sb[k], s_band)
-                                      : (ri[k] == kRasterFull ? kPixMixed : kPixEmpty);
+          if (IS == MGPU_BNG && bng_grid)
+            cl[k] = ri[k] == kRasterFull ? kPixMixed : (ri[k] == kNoPixel ? kPixEmpty : ri[k]);
+          else
+            cl[k] = ri[k] < kRasterFull ? raster_class_blk(t, s_blk, ri[k], bi[k], sb[k], s_band)
+                                        : (ri[k] == kRasterFull ? kPixMixed : kPixEmpty);
 #endif
-        if (IS == MGPU_BNG && bng_grid) ge[k] = gix[k];  // (the first chip)
-        else ge[k] = (IS == MGPU_BNG && ri[k] < kRasterFull) ? t.grid[gix[k]] : 0ull;
+          if (IS == MGPU_BNG && bng_grid) ge[k] = gix[k];  // (the first chip)
+          else ge[k] = (IS == MGPU_BNG && ri[k] < kRasterFull) ? t.grid[gix[k]] : 0ull;
+        }
       }
 #pragma unroll
       for (int k = 0; k < kCfyBatch; k++) {
         const int64_t p = c0 + (int64_t)(b + k) * 64 + lane;
-        const bool valid = p < a.n;
+        const bool valid = kFull || p < a.n;
         bool mixed = cl[k] == kPixMixed;
         Code code;
         if (IS == MGPU_H3) {
@@ -1461,7 +1538,17 @@ __global__ __launch_bounds__(kCfyBlock) __attribute__((amdgpu_waves_per_eu(MGPU_
       sa.chunk_mixed[ch] = nmixed;
       a.group_cand[ch] = 0;  // (the mixed tiles add to it, after this kernel on the stream)
     }
-  }
+  };
+  auto run = [&](auto staged_c, auto nulls_c) {
+    for (int64_t ch = (int64_t)blockIdx.x * kW + wave; ch < n_chunks; ch += ch_step) {
+      if (IS == MGPU_H3 && (ch + 1) * kChunk <= a.n) {
+        if constexpr (IS == MGPU_H3) run_chunk(ch, staged_c, nulls_c, std::true_type{});
+      } else {
+        run_chunk(ch, staged_c, nulls_c, std::false_type{});
+      }
+    }
+  };
+  cfy_dispatch<IS>(cfy_staged(t, nblk), a.valid != nullptr, run);
   count_wave(&a.counters[2], any_bad);
 }
 
@@ -1501,7 +1588,11 @@ __global__ __launch_bounds__(kCfyBlock) __attribute__((amdgpu_waves_per_eu(MGPU_
   const unsigned long long below = (1ull << lane) - 1ull;
   bool any_bad = false;
   const int64_t ch_step = (int64_t)gridDim.x * kW;
-  for (int64_t ch = (int64_t)blockIdx.x * kW + wave; ch < n_chunks; ch += ch_step) {
+  // One chunk; kStaged, kNulls, kFull as in classify_wave_kernel.  (With the bounds test the
+  // batch's items load one after the other: the tail's 8-byte loads reuse the registers
+  // and the two paths' waits merge -- a full chunk has neither.)
+  auto run_chunk = [&](int64_t ch, auto staged_c, auto nulls_c, auto full_c) {
+    constexpr bool kStaged = decltype(staged_c)::value, kNulls = decltype(nulls_c)::value, kFull = decltype(full_c)::value;
     const int64_t c0 = ch * kChunk;
     uint32_t pairs = 0, nmixed = 0;
     for (int b = 0; b < kPairItems; b += kPB) {
@@ -1509,7 +1600,7 @@ __global__ __launch_bounds__(kCfyBlock) __attribute__((amdgpu_waves_per_eu(MGPU_
 #pragma unroll
       for (int k = 0; k < kPB; k++) {
         const int64_t p = c0 + (int64_t)(b + k) * 128 + 2 * lane;
-        if (p + 1 < a.n) {
+        if (kFull || p + 1 < a.n) {
           const dbl2_t vx = __builtin_nontemporal_load((const dbl2_t*)(a.x + p));
           const dbl2_t vy = __builtin_nontemporal_load((const dbl2_t*)(a.y + p));
           X[2 * k] = vx.x, X[2 * k + 1] = vx.y, Y[2 * k] = vy.x, Y[2 * k + 1] = vy.y;
@@ -1526,7 +1617,7 @@ __global__ __launch_bounds__(kCfyBlock) __attribute__((amdgpu_waves_per_eu(MGPU_
         sb[j] = 0;
         bi[j] = kNoPixel;
         const int64_t pj = c0 + (int64_t)(b + j / 2) * 128 + 2 * lane + (j & 1);
-        if (pj < a.n && pt_valid(a.valid, a.valid_off, pj)) {
+        if ((kFull || pj < a.n) && (!kNulls || pt_valid(a.valid, a.valid_off, pj))) {
           bool ok = true;
           uint32_t g_ = 0, s_ = 0, b_ = kNoPixel;
           if (IS == MGPU_BNG && bng_grid) {
@@ -1544,15 +1635,21 @@ __global__ __launch_bounds__(kCfyBlock) __attribute__((amdgpu_waves_per_eu(MGPU_
       }
       uint32_t cl[kPts];
       uint64_t ge[kPts];
+      if constexpr (kStaged) {
+        raster_class_batch<kPts>(t, s_blk, s_band, ri, bi, sb, cl);
 #pragma unroll
-      for (int j = 0; j < kPts; j++) {
-        if (IS == MGPU_BNG && bng_grid) {
-          cl[j] = ri[j] == kRasterFull ? kPixMixed : (ri[j] == kNoPixel ? kPixEmpty : ri[j]);
-          ge[j] = gix[j];  // (the first chip)
-        } else {
-          cl[j] = ri[j] < kRasterFull ? raster_class_blk(t, s_blk, ri[j], bi[j], sb[j], s_band)
-                                      : (ri[j] == kRasterFull ? kPixMixed : kPixEmpty);
-          ge[j] = (IS == MGPU_BNG && ri[j] < kRasterFull) ? t.grid[gix[j]] : 0ull;
+        for (int j = 0; j < kPts; j++) ge[j] = 0ull;
+      } else {
+#pragma unroll
+        for (int j = 0; j < kPts; j++) {
+          if (IS == MGPU_BNG && bng_grid) {
+            cl[j] = ri[j] == kRasterFull ? kPixMixed : (ri[j] == kNoPixel ? kPixEmpty : ri[j]);
+            ge[j] = gix[j];  // (the first chip)
+          } else {
+            cl[j] = ri[j] < kRasterFull ? raster_class_blk(t, s_blk, ri[j], bi[j], sb[j], s_band)
+                                        : (ri[j] == kRasterFull ? kPixMixed : kPixEmpty);
+            ge[j] = (IS == MGPU_BNG && ri[j] < kRasterFull) ? t.grid[gix[j]] : 0ull;
+          }
         }
       }
       Code code[kPts];
@@ -1574,12 +1671,12 @@ __global__ __launch_bounds__(kCfyBlock) __attribute__((amdgpu_waves_per_eu(MGPU_
           code[j] = (Code)(m ? kCodeMixed32 : (mm ? (first << 8) | mm : 0u));
           if (!m) pairs += __popc(mm);
         }
-        mixed[j] = m && pj < a.n;
+        mixed[j] = m && (kFull || pj < a.n);
       }
 #pragma unroll
       for (int k = 0; k < kPB; k++) {
         const int64_t p = c0 + (int64_t)(b + k) * 128 + 2 * lane;
-        if (p + 1 < a.n) {
+        if (kFull || p + 1 < a.n) {
           if (sizeof(Code) == 2) {
             MGPU_ST_INTER((uint32_t)code[2 * k] | ((uint32_t)code[2 * k + 1] << 16), (uint32_t*)(codes + p));
           } else {
@@ -1606,7 +1703,17 @@ __global__ __launch_bounds__(kCfyBlock) __attribute__((amdgpu_waves_per_eu(MGPU_
       sa.chunk_mixed[ch] = nmixed;
       a.group_cand[ch] = 0;  // (the mixed tiles add to it, after this kernel on the stream)
     }
-  }
+  };
+  auto run = [&](auto staged_c, auto nulls_c) {
+    for (int64_t ch = (int64_t)blockIdx.x * kW + wave; ch < n_chunks; ch += ch_step) {
+      if (IS == MGPU_H3 && (ch + 1) * kChunk <= a.n) {
+        if constexpr (IS == MGPU_H3) run_chunk(ch, staged_c, nulls_c, std::true_type{});
+      } else {
+        run_chunk(ch, staged_c, nulls_c, std::false_type{});
+      }
+    }
+  };
+  cfy_dispatch<IS>(cfy_staged(t, nblk), a.valid != nullptr, run);
   count_wave(&a.counters[2], any_bad);
 }
 
