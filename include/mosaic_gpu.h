@@ -117,6 +117,11 @@ int32_t mgpu_ctx_destroy(mgpu_ctx* ctx);
  *                     joins through the split pipeline with the grid entry as the code (a
  *                     cell of core chips, or an answer-grid square, answers its points; the
  *                     rest go to the mixed tiles) / through the fused pipeline
+ *   "cfy_fine"        1 (default) / 0, read by each join: the split pipeline's classify pass
+ *                     answers from the table's finer byte-coded block table (derived at upload
+ *                     for H3 tables with a block table, row bands and a second level, when a
+ *                     shape finer than 8 x 8 pixels fits the LDS) / from the 8 x 8 block table,
+ *                     as for a table without one.  The pairs are the same either way
  *   "count_lds_slots" mgpu_pip_join_count keeps per-workgroup LDS histograms for chip tables
  *                     of at most this many polygons (default and maximum 4096: 48 KiB of
  *                     counts and sums per workgroup, two workgroups per CU); larger tables go through a
@@ -806,6 +811,16 @@ int32_t mgpu_test_decode_point(int32_t format, const uint8_t* data, int64_t len,
  * points, candidates, ...; builds with -DMGPU_STAMPS add per-phase clock ticks of the
  * join tiles at [10..14]).  Waits for the device. */
 int32_t mgpu_test_join_counters(mgpu_ctx* ctx, uint64_t* out16);
+/* TEST ONLY: the classify kernels' finer block table of an uploaded table (derived on the
+ * device when the table is adopted).  dims[7] = raster_nx, raster_ny, the block shifts sx
+ * and sy, the table's columns and rows, and 1 when the table has one (else the four before
+ * it are 0).  geom[8] (or NULL) = the pixel grid's origin x0, y0 and scales 1 / dx, 1 / dy
+ * (pixel = ((lon - x0) / dx, (lat - y0) / dy) truncated, clamped to the last one) and the
+ * table's box lon_min, lat_min, lon_max, lat_max.  out_classes (or NULL): the raster_ny *
+ * raster_nx 16-bit pixel classes the table was derived from; out_fine (or NULL): its rows *
+ * columns bytes -- both host arrays, row-major. */
+int32_t mgpu_test_fine_table(const mgpu_chips* chips, int64_t* dims, double* geom, uint16_t* out_classes,
+                             uint8_t* out_fine);
 /* TEST ONLY: the host part of mgpu_chips_polygons (poly_slots.h) -- the distinct values
  * of polygon_id[n] ascending into out_ids (room for n), *out_n their number, and
  * out_slot_of_row[i] = the slot of polygon_id[i]. */

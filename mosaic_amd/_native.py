@@ -45,7 +45,7 @@ EXPORTS = (
     "mgpu_test_receive_blob", "mgpu_ring_join", "mgpu_ring_join_ex", "mgpu_ring_join_final",
     "mgpu_test_overlay_verify",
     "mgpu_chips_polygons", "mgpu_pip_join_count", "mgpu_test_poly_slots_host", "mgpu_chips_raster_info",
-    "mgpu_pip_join_lookup",
+    "mgpu_pip_join_lookup", "mgpu_test_fine_table",
     "mgpu_cell_agg_create", "mgpu_cell_agg_add_points", "mgpu_cell_agg_add_cells", "mgpu_cell_agg_add_counted",
     "mgpu_cell_agg_size", "mgpu_cell_agg_fetch", "mgpu_cell_agg_clear", "mgpu_cell_agg_destroy",
     "mgpu_cells_to_centers", "mgpu_cells_to_boundaries", "mgpu_cells_boundary_wkb", "mgpu_cells_area",
@@ -195,6 +195,7 @@ def lib():
                                                   ctypes.POINTER(MgpuStats)]),
         "mgpu_test_internal_centroid": (I32, [I64, P, P, P, P, P, P, P, P]),
         "mgpu_test_join_counters": (I32, [P, P]),
+        "mgpu_test_fine_table": (I32, [P, P, P, P, P]),
         "mgpu_test_receive_blob": (I32, [P, P, I32, ctypes.POINTER(P)]),
         "mgpu_chips_polygons": (I32, [P, P, I64, ctypes.POINTER(I64)]),
         "mgpu_pip_join_count": (I32, [P, P, I32, I32, P, P, P, I64, I64, P, P, I32, P, ctypes.POINTER(MgpuStats)]),

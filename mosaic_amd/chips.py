@@ -91,6 +91,23 @@ class DeviceChips:
         return {"chips": a.value, "cells": b.value, "vertices": c.value, "bytes": n, "raster_mode": m.value,
                 "raster_ncls": k.value}
 
+    def fine_table(self):
+        """The classify kernels' finer block table (mgpu_test_fine_table; a test hook): a dict
+        of the pixel classes it was derived from, ``classes`` [ny, nx] uint16 (None: the
+        table has no lon/lat pixel index), the block shifts ``sx`` and ``sy``, and its bytes
+        ``fine`` [rows, columns] uint8 -- None when the table has none; ``x0, y0, inv_dx,
+        inv_dy``: the pixel grid, and ``bbox``: the table's box."""
+        d, g = np.zeros(7, np.int64), np.zeros(8, np.float64)
+        N.check(N.lib().mgpu_test_fine_table(self.handle, d.ctypes.data, g.ctypes.data, None, None))
+        nx, ny, sx, sy, bnx, bny, built = (int(v) for v in d)
+        classes = np.zeros((ny, nx), np.uint16) if nx * ny else None
+        fine = np.zeros((bny, bnx), np.uint8) if built else None
+        N.check(N.lib().mgpu_test_fine_table(self.handle, d.ctypes.data, None,
+                                             None if classes is None else classes.ctypes.data,
+                                             None if fine is None else fine.ctypes.data))
+        return {"classes": classes, "sx": sx, "sy": sy, "fine": fine, "x0": g[0], "y0": g[1], "inv_dx": g[2],
+                "inv_dy": g[3], "bbox": tuple(g[4:])}
+
     def polygons(self):
         """The table's distinct polygon ids, ascending (int32 numpy array; mgpu_chips_polygons):
         slot k of pip_join_count's arrays is polygons()[k]."""

@@ -38,7 +38,7 @@ class GpuContext:
     def set_option(self, key, value):
         """mgpu_ctx_set_option: the planner and tuning options of this context (keys in
         include/mosaic_gpu.h: h3_libm, pipeline, bin_count, bin_min_mb, bin_min_points,
-        bin_xcd, spin_us, count_lds_slots, count_groups, cellagg_groups, cellagg_lds, cellagg_bin_min, kring_batch, polyfill_slab, geomring_slab, geomring_lds_slots, raster, raster_bng, raster_sub, raster_milli)."""
+        bin_xcd, spin_us, cfy_fine, count_lds_slots, count_groups, cellagg_groups, cellagg_lds, cellagg_bin_min, kring_batch, polyfill_slab, geomring_slab, geomring_lds_slots, raster, raster_bng, raster_sub, raster_milli)."""
         N.check(N.lib().mgpu_ctx_set_option(self.handle, key.encode(), int(value)))
 
     def get_option(self, key):

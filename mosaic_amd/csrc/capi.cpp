@@ -319,6 +319,9 @@ int32_t mgpu_ctx_set_option(mgpu_ctx* ctx, const char* key, int64_t v) {
   } else if (k == "bng_split") {
     if (v != 0 && v != 1) return bad();
     o.bng_split = v;
+  } else if (k == "cfy_fine") {
+    if (v != 0 && v != 1) return bad();
+    o.cfy_fine = v;
   } else if (k == "count_lds_slots") {
     if (v < 0 || v > mgpu::kCountLdsSlotsMax) return bad();
     o.count_lds_slots = v;
@@ -371,7 +374,7 @@ int32_t mgpu_ctx_get_option(const mgpu_ctx* ctx, const char* key, int64_t* v) {
       {"h3_libm", o.h3_libm},       {"pipeline", o.pipeline}, {"bin_count", o.bin_count},
       {"bin_min_mb", o.bin_min_mb}, {"bin_min_points", o.bin_min_points}, {"bin_xcd", o.bin_xcd},
       {"bin_keys", o.bin_keys},     {"spin_us", o.spin_us},   {"ring_batch", o.ring_batch},       {"raster", o.raster},     {"raster_bng", o.raster_bng},
-      {"bng_split", o.bng_split},   {"count_lds_slots", o.count_lds_slots}, {"count_groups", o.count_groups},
+      {"bng_split", o.bng_split},   {"cfy_fine", o.cfy_fine}, {"count_lds_slots", o.count_lds_slots}, {"count_groups", o.count_groups},
       {"kring_batch", o.kring_batch}, {"cellagg_groups", o.cellagg_groups}, {"cellagg_lds", o.cellagg_lds}, {"cellagg_bin_min", o.cellagg_bin_min},
       {"raster_sub", o.raster_sub}, {"raster_milli", o.raster_milli}, {"polyfill_slab", o.polyfill_slab},
       {"geomring_slab", o.geomring_slab}, {"geomring_lds_slots", o.geomring_lds_slots}};
@@ -607,6 +610,24 @@ int32_t adopt_device_blob(mgpu_ctx* ctx, void* dev_blob, int64_t bytes, mgpu_chi
   ch->index_system = hdr.index_system;
   ch->view = view_from_header(hdr, (uint8_t*)ch->blob);
   ch->n_vertices = hdr.n_vertices;
+  // the classify kernels' finer block table, derived from the blob's pixel classes and kept
+  // on the handle beside the blob (the blob's own bytes are pinned: every way a table
+  // reaches a device passes through here)
+  uint32_t sx = 0, sy = 0, bnx = 0, bny = 0;
+  if (ch->index_system == MGPU_H3 && fine_table_shape(ch->view, &sx, &sy, &bnx, &bny)) {
+    void* fine = nullptr;
+    hipError_t e = hipMalloc(&fine, ((size_t)bnx * bny + 3) & ~(size_t)3);
+    if (e == hipSuccess) e = launch_fine_table(ch->view, sx, sy, bnx, bny, (uint8_t*)fine, nullptr);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) {
+      if (fine) hipFree(fine);
+      delete ch;
+      return fail(MGPU_E_DEVICE, "fine block table: %s", hipGetErrorString(e));
+    }
+    ch->fine = fine;
+    ch->view.raster_fine = (const uint8_t*)fine;
+    ch->view.fine_sx = sx, ch->view.fine_sy = sy, ch->view.fine_bnx = bnx, ch->view.fine_bny = bny;
+  }
   *out = ch;
   return MGPU_OK;
 }
@@ -770,6 +791,7 @@ int32_t mgpu_chips_destroy(mgpu_chips* chips) {
   if (!chips) return MGPU_OK;
   hipSetDevice(chips->device);
   if (chips->blob) hipFree(chips->blob);
+  if (chips->fine) hipFree(chips->fine);
   free_poly_slots(chips);
   delete chips;
   return MGPU_OK;
@@ -912,6 +934,7 @@ static int32_t join_impl(mgpu_ctx* ctx, const mgpu_chips* chips, int32_t is, int
   a.res = res;
   a.res_match = (is == MGPU_BNG || chips->view.res < 0 || chips->view.res == res) ? 1 : 0;
   a.chips = chips->view;
+  if (!o.cfy_fine) a.chips.raster_fine = nullptr;  // (the classify kernels then stage raster_blk)
   a.counters = (unsigned long long*)base;
   a.pool_used = a.counters + 5;
   a.n_dirty = (uint32_t*)(a.counters + 6);
@@ -1858,6 +1881,26 @@ int32_t mgpu_test_join_counters(mgpu_ctx* ctx, uint64_t* out16) {
   if (int32_t st = set_device(ctx->device)) return st;
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(out16, ctx->ws, 16 * 8, hipMemcpyDeviceToHost));
+  return MGPU_OK;
+}
+
+int32_t mgpu_test_fine_table(const mgpu_chips* chips, int64_t* dims, double* geom, uint16_t* out_classes,
+                             uint8_t* out_fine) {
+  if (!chips || !dims) return fail(MGPU_E_INVALID_ARG, "bad arguments");
+  if (int32_t st = set_device(chips->device)) return st;
+  const mgpu::ChipTableView& v = chips->view;
+  const bool lonlat = v.raster_mode == mgpu::kRasterLonLat;
+  const int64_t d[7] = {lonlat ? v.raster_nx : 0, lonlat ? v.raster_ny : 0, v.fine_sx, v.fine_sy, v.fine_bnx, v.fine_bny,
+                        v.raster_fine ? 1 : 0};
+  memcpy(dims, d, sizeof d);
+  if (geom) {
+    const double g[8] = {v.raster_x0, v.raster_y0, v.raster_inv_dx, v.raster_inv_dy, v.bbox[0], v.bbox[1], v.bbox[2], v.bbox[3]};
+    memcpy(geom, g, sizeof g);
+  }
+  if (out_classes && d[0] * d[1])
+    HIP_TRY(hipMemcpy(out_classes, v.raster, (size_t)(d[0] * d[1]) * 2, hipMemcpyDeviceToHost));
+  if (out_fine && v.raster_fine)
+    HIP_TRY(hipMemcpy(out_fine, v.raster_fine, (size_t)(d[4] * d[5]), hipMemcpyDeviceToHost));
   return MGPU_OK;
 }
 

@@ -30,6 +30,7 @@ struct mgpu_options {
   int64_t geomring_slab = (int64_t)1 << 16;  // mgpu_geometry_kring: border cells whose ring lists are held in scratch at a time
   int64_t geomring_lds_slots = 0;         // ... slots of a geometry's LDS set (0: the default and maximum, geom_ring.h kLdsSlots; a test hook)
   int64_t bng_split = 0;                  // BNG dense tables: the split pipeline, the grid entry as the code (A/B r6: C4 2.43 vs 2.17 ms fused -- off)
+  int64_t cfy_fine = 1;                   // split pipeline: classify from the table's finer byte-coded block table when it has one (0: from raster_blk)
   // the chip-table builder of mgpu_chips_upload on this context (mgpu_build_opts)
   int64_t raster = 1, raster_bng = 0, raster_sub = 16, raster_milli = 250;
 };
@@ -107,6 +108,8 @@ struct mgpu_chips {
   // mgpu_pip_join_count's id -> slot table (capi.cpp PolySlotsDev), built at the first use
   // from chip_poly and kept outside the blob
   mutable void* slots = nullptr;
+  // view.raster_fine's device allocation (capi.cpp adopt_device_blob), or null
+  void* fine = nullptr;
 };
 
 namespace mgpu {

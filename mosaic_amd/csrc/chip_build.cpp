@@ -48,7 +48,7 @@ size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 namespace mgpu {
 mgpu::ChipTableView view_from_header(const BlobHeader& h, uint8_t* base) {
-  mgpu::ChipTableView v;
+  mgpu::ChipTableView v{};  // (raster_fine: none -- capi.cpp adopt_device_blob derives it)
   v.slots = (const mgpu::HashSlot*)(base + h.off[kArrSlots]);
   v.hash_mask = h.hash_mask;
   v.max_probe = h.max_probe;

@@ -217,7 +217,17 @@ struct ChipTableView {
   // bshift = 0: none
   uint32_t raster_bshift, raster_bnx, raster_bny;
   const uint16_t* raster_blk;
+  // lonlat, derived from `raster` on the device when the table is adopted (kernels.hip
+  // launch_fine_table; not part of the blob, owned by the mgpu_chips handle): blocks of
+  // 2^fine_sx x 2^fine_sy pixels, one byte each, raster_fine[(iy >> fine_sy) * fine_bnx +
+  // (ix >> fine_sx)] = the class all of the block's pixels share when that class is below
+  // kFineLookup (classes are numbered by match count, the common ones first), else
+  // kFineLookup: the point's class is looked up as without this table.  The classify
+  // kernels hold it in LDS instead of raster_blk.  null: none
+  uint32_t fine_sx, fine_sy, fine_bnx, fine_bny;
+  const uint8_t* raster_fine;
 };
+constexpr uint32_t kFineLookup = 0xFFu;
 
 enum RasterMode { kRasterNone = 0, kRasterLonLat = 1, kRasterBng = 2 };
 constexpr uint32_t kCellAnsChips = 15;      // chips of a cell with an answer grid, at most

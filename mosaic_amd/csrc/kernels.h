@@ -109,6 +109,12 @@ int64_t split_chunks(int64_t n);
 hipError_t launch_split(int is, const SplitArgs& a, hipStream_t s, hipEvent_t after_classify, hipEvent_t after_mixed,
                         bool emit = true);
 hipError_t launch_split_emit(int is, const SplitArgs& a, hipStream_t s);
+// The classify kernels' finer block table (chip_table.h raster_fine).  fine_table_shape: whether
+// `t` gets one and its block shifts and dimensions; launch_fine_table writes its bny * bnx
+// bytes (and the padding up to a multiple of four) to `out` on the device.
+bool fine_table_shape(const ChipTableView& t, uint32_t* sx, uint32_t* sy, uint32_t* bnx, uint32_t* bny);
+hipError_t launch_fine_table(const ChipTableView& t, uint32_t sx, uint32_t sy, uint32_t bnx, uint32_t bny, uint8_t* out,
+                             hipStream_t s);
 // the override passes (kernels.hip launch_join_redo): the split pipeline's over R.list's n chunks
 hipError_t launch_split_redo(int is, const SplitArgs& sa, const RedoArgs& R, int64_t n, hipStream_t s,
                              bool emit = true);

@@ -1349,7 +1349,10 @@ constexpr int kCfyBatch = MGPU_CFY_BATCH;
 // result is selected afterwards, so a batch costs two round trips, not 2 N.  cl[k] is bit
 // for bit raster_class_blk's answer (kPixEmpty / kPixMixed for ri = kNoPixel /
 // kRasterFull); an invalid point comes with ri = bi = kNoPixel, sub = 0.
-template <int N>
+// FINE: blk is the LDS copy of raster_fine (chip_table.h) and bi the point's block there: a
+// byte below kFineLookup is the class of every pixel of the block -- what the pixel load
+// would have returned -- and kFineLookup sends the lane through the same two stages.
+template <int N, bool FINE = false>
 __device__ __forceinline__ void raster_class_batch(const ChipTableView& t, const uint16_t* blk, const uint32_t* band,
                                                    const uint32_t (&ri)[N], const uint32_t (&bi)[N],
                                                    const uint32_t (&sub)[N], uint32_t (&cl)[N]) {
@@ -1358,12 +1361,13 @@ __device__ __forceinline__ void raster_class_batch(const ChipTableView& t, const
   bool pix[N], ref[N];
 #pragma unroll
   for (int k = 0; k < N; k++) {
-    c[k] = blk[bi[k] != kNoPixel ? bi[k] : 0u];
+    const uint32_t i = bi[k] != kNoPixel ? bi[k] : 0u;
+    c[k] = FINE ? (uint32_t)((const uint8_t*)blk)[i] : (uint32_t)blk[i];
     bb[k] = band[sub[k] >> 16];  // (the point's row band, 0 for an invalid point)
   }
 #pragma unroll
   for (int k = 0; k < N; k++) {
-    pix[k] = ri[k] < kRasterFull && (bi[k] == kNoPixel || c[k] == kPixMixed);
+    pix[k] = ri[k] < kRasterFull && (bi[k] == kNoPixel || c[k] == (FINE ? kFineLookup : (uint32_t)kPixMixed));
     px[k] = t.raster[pix[k] ? ri[k] : 0u];
   }
 #pragma unroll
@@ -1383,9 +1387,28 @@ __device__ __forceinline__ void raster_class_batch(const ChipTableView& t, const
 // (raster_sub_n), and the blob gives every array at least one zero-padded 256-byte slot
 // (chip_build.cpp layout_blob), so its index 0 is readable even when no pixel is refined
 // -- no lane selects what it read there.
-__device__ __forceinline__ bool cfy_staged(const ChipTableView& t, uint32_t nblk) {
+__host__ __device__ __forceinline__ bool cfy_staged(const ChipTableView& t, uint32_t nblk) {
   return t.raster_blk && nblk && t.raster_band && t.raster_nband && !t.raster_pal && t.raster_sub && t.raster_sub_n &&
          t.raster_nx && t.raster_ny;
+}
+
+// The finer block table (chip_table.h raster_fine) is derived for the tables cfy_staged
+// accepts, in the finest block shape -- 4x4, 8x4 or 4x8 pixels -- whose bytes plus the row
+// bands fit the LDS of one workgroup of the launch shape that uses it.  (8x8 is what
+// raster_blk already answers: nothing is derived then.)
+// Launch shapes, both 24 waves per CU (6 per SIMD, 80 VGPRs): 512 threads, three workgroups
+// per CU, 53 KB each (8x4 on the NYC res-9 table); 768 threads, two per CU, 79 KB each (4x4).
+// (A/B r11, profiles/r11/bench_ab.jsonl, C2 classify: parent 0.558 ms, 512 threads 0.551,
+// 768 threads 0.538 -- 4x4 blocks answer 68.7% of the points from LDS, 8x4 64.2%, 8x8 62.1%.)
+#ifndef MGPU_CFY_FINE_BLOCK
+#define MGPU_CFY_FINE_BLOCK 768
+#endif
+constexpr int kCfyFineBlock = MGPU_CFY_FINE_BLOCK;
+static_assert(kCfyFineBlock == 512 || kCfyFineBlock == 768, "the fine classify kernels' launch shapes");
+constexpr size_t kCfyFineLds = kCfyFineBlock == 512 ? 53 * 1024 : 79 * 1024;
+constexpr int kCfyFineWaves = kCfyFineBlock == 768 ? 6 : MGPU_CFY_WAVES;  // (768: two workgroups need 6 waves per SIMD)
+__host__ __device__ __forceinline__ size_t cfy_fine_lds(uint32_t nfine, uint32_t nband) {
+  return (((size_t)nfine + 3) & ~(size_t)3) + (size_t)nband * 4;
 }
 
 // run(staged, nulls) with both switches as compile-time constants.  BNG keeps the one
@@ -1405,24 +1428,31 @@ __device__ __forceinline__ void cfy_dispatch(bool staged, bool nulls, F& run) {
   }
 }
 
-template <int IS>
-__global__ __launch_bounds__(kCfyBlock) __attribute__((amdgpu_waves_per_eu(MGPU_CFY_WAVES))) void classify_wave_kernel(SplitArgs sa, int64_t n_chunks) {
+// BLOCK: threads per workgroup.  FINE (H3, launched only for a table with raster_fine, which
+// cfy_staged accepts): the LDS table is raster_fine's bytes, copied a word at a time (the
+// allocation is padded to whole words), and every chunk runs the staged form.
+template <int IS, int BLOCK = kCfyBlock, bool FINE = false>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(FINE ? kCfyFineWaves : MGPU_CFY_WAVES))) void classify_wave_kernel(SplitArgs sa, int64_t n_chunks) {
   using Code = typename CodeOf<IS>::T;
-  constexpr int kW = kCfyBlock / 64;        // waves per workgroup
+  static_assert(!FINE || IS == MGPU_H3, "raster_fine is a lonlat table");
+  constexpr int kW = BLOCK / 64;            // waves per workgroup
   constexpr int kItems = kChunk / 64;       // points per lane per chunk
   static_assert(kItems % kCfyBatch == 0, "MGPU_CFY_BATCH must divide the points per lane of a chunk");
   const JoinArgs& a = sa.j;
   const ChipTableView& t = a.chips;
   extern __shared__ uint16_t s_blk[];       // [raster_bny * raster_bnx] (IS == H3), then the row bands
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const bool use_blk = IS == MGPU_H3 && t.raster_blk != nullptr;
+  const bool use_blk = IS == MGPU_H3 && (FINE || t.raster_blk != nullptr);
   const bool bng_grid = IS == MGPU_BNG && t.raster_mode == kRasterNone;  // (bng_grid_class)
-  const uint32_t nblk = use_blk ? t.raster_bnx * t.raster_bny : 0u;
-  uint32_t* s_band = (uint32_t*)(s_blk + ((nblk + 1) & ~1u));
-  if (use_blk)
-    for (uint32_t i = threadIdx.x; i < nblk; i += kCfyBlock) s_blk[i] = t.raster_blk[i];
+  const uint32_t nblk = use_blk ? (FINE ? t.fine_bnx * t.fine_bny : t.raster_bnx * t.raster_bny) : 0u;
+  uint32_t* s_band = FINE ? (uint32_t*)s_blk + ((nblk + 3) >> 2) : (uint32_t*)(s_blk + ((nblk + 1) & ~1u));
+  if (FINE) {
+    for (uint32_t i = threadIdx.x; i < ((nblk + 3) >> 2); i += BLOCK) ((uint32_t*)s_blk)[i] = ((const uint32_t*)t.raster_fine)[i];
+  } else if (use_blk) {
+    for (uint32_t i = threadIdx.x; i < nblk; i += BLOCK) s_blk[i] = t.raster_blk[i];
+  }
   if (IS == MGPU_H3)
-    for (uint32_t i = threadIdx.x; i < t.raster_nband; i += kCfyBlock) s_band[i] = t.raster_band[i];
+    for (uint32_t i = threadIdx.x; i < t.raster_nband; i += BLOCK) s_band[i] = t.raster_band[i];
   __syncthreads();
   Code* codes = (Code*)sa.codes;
   const unsigned long long below = (1ull << lane) - 1ull;
@@ -1463,7 +1493,7 @@ __global__ __launch_bounds__(kCfyBlock) __attribute__((amdgpu_waves_per_eu(MGPU_
             const uint32_t m = bng_grid_class(a, pk, bx[k], by[k], &ok, &g_);
             ri[k] = m == kPixMixed ? kRasterFull : m;  // (the class itself, below)
           } else {
-            ri[k] = raster_index<IS>(t, bx[k], by[k], &ok, &g_, &s_, &b_);  // (see classify_pair_kernel)
+            ri[k] = raster_index<IS, FINE>(t, bx[k], by[k], &ok, &g_, &s_, &b_);  // (see classify_pair_kernel)
           }
           gix[k] = g_;
           sb[k] = s_;
@@ -1477,7 +1507,7 @@ __global__ __launch_bounds__(kCfyBlock) __attribute__((amdgpu_waves_per_eu(MGPU_
 #define MGPU_CFY_ABLATE 0  // profiling only (wrong answers): 1 no lookups, 2 LDS blocks only, 3 no sub-pixels
 #endif
       if constexpr (kStaged) {
-        raster_class_batch<kCfyBatch>(t, s_blk, s_band, ri, bi, sb, cl);
+        raster_class_batch<kCfyBatch, FINE>(t, s_blk, s_band, ri, bi, sb, cl);
 #pragma unroll
         for (int k = 0; k < kCfyBatch; k++) ge[k] = 0ull;
       } else {
@@ -1548,7 +1578,12 @@ __global__ __launch_bounds__(kCfyBlock) __attribute__((amdgpu_waves_per_eu(MGPU_
       }
     }
   };
-  cfy_dispatch<IS>(cfy_staged(t, nblk), a.valid != nullptr, run);
+  if constexpr (FINE) {
+    if (a.valid != nullptr) run(std::true_type{}, std::true_type{});
+    else run(std::true_type{}, std::false_type{});
+  } else {
+    cfy_dispatch<IS>(cfy_staged(t, nblk), a.valid != nullptr, run);
+  }
   count_wave(&a.counters[2], any_bad);
 }
 
@@ -1563,10 +1598,11 @@ __global__ __launch_bounds__(kCfyBlock) __attribute__((amdgpu_waves_per_eu(MGPU_
 #define MGPU_CFY_PAIR 1
 #endif
 typedef double dbl2_t __attribute__((ext_vector_type(2)));
-template <int IS>
-__global__ __launch_bounds__(kCfyBlock) __attribute__((amdgpu_waves_per_eu(MGPU_CFY_WAVES))) void classify_pair_kernel(SplitArgs sa, int64_t n_chunks) {
+template <int IS, int BLOCK = kCfyBlock, bool FINE = false>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(FINE ? kCfyFineWaves : MGPU_CFY_WAVES))) void classify_pair_kernel(SplitArgs sa, int64_t n_chunks) {
   using Code = typename CodeOf<IS>::T;
-  constexpr int kW = kCfyBlock / 64;
+  static_assert(!FINE || IS == MGPU_H3, "raster_fine is a lonlat table");
+  constexpr int kW = BLOCK / 64;
   constexpr int kPairItems = kChunk / 128;                       // pair items per lane per chunk
   constexpr int kPB = kCfyBatch / 2 > 0 ? kCfyBatch / 2 : 1;      // pair items in flight
   constexpr int kPts = 2 * kPB;
@@ -1575,14 +1611,17 @@ __global__ __launch_bounds__(kCfyBlock) __attribute__((amdgpu_waves_per_eu(MGPU_
   const ChipTableView& t = a.chips;
   extern __shared__ uint16_t s_blk[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const bool use_blk = IS == MGPU_H3 && t.raster_blk != nullptr;
+  const bool use_blk = IS == MGPU_H3 && (FINE || t.raster_blk != nullptr);
   const bool bng_grid = IS == MGPU_BNG && t.raster_mode == kRasterNone;  // (bng_grid_class)
-  const uint32_t nblk = use_blk ? t.raster_bnx * t.raster_bny : 0u;
-  uint32_t* s_band = (uint32_t*)(s_blk + ((nblk + 1) & ~1u));
-  if (use_blk)
-    for (uint32_t i = threadIdx.x; i < nblk; i += kCfyBlock) s_blk[i] = t.raster_blk[i];
+  const uint32_t nblk = use_blk ? (FINE ? t.fine_bnx * t.fine_bny : t.raster_bnx * t.raster_bny) : 0u;
+  uint32_t* s_band = FINE ? (uint32_t*)s_blk + ((nblk + 3) >> 2) : (uint32_t*)(s_blk + ((nblk + 1) & ~1u));
+  if (FINE) {  // (classify_wave_kernel)
+    for (uint32_t i = threadIdx.x; i < ((nblk + 3) >> 2); i += BLOCK) ((uint32_t*)s_blk)[i] = ((const uint32_t*)t.raster_fine)[i];
+  } else if (use_blk) {
+    for (uint32_t i = threadIdx.x; i < nblk; i += BLOCK) s_blk[i] = t.raster_blk[i];
+  }
   if (IS == MGPU_H3)
-    for (uint32_t i = threadIdx.x; i < t.raster_nband; i += kCfyBlock) s_band[i] = t.raster_band[i];
+    for (uint32_t i = threadIdx.x; i < t.raster_nband; i += BLOCK) s_band[i] = t.raster_band[i];
   __syncthreads();
   Code* codes = (Code*)sa.codes;
   const unsigned long long below = (1ull << lane) - 1ull;
@@ -1625,7 +1664,7 @@ __global__ __launch_bounds__(kCfyBlock) __attribute__((amdgpu_waves_per_eu(MGPU_
             ri[j] = m == kPixMixed ? kRasterFull : m;
           } else {
             // (always a local's address: a pointer chosen at run time put b_ in scratch)
-            ri[j] = raster_index<IS>(t, X[j], Y[j], &ok, &g_, &s_, &b_);
+            ri[j] = raster_index<IS, FINE>(t, X[j], Y[j], &ok, &g_, &s_, &b_);
           }
           gix[j] = g_;
           sb[j] = s_;
@@ -1636,7 +1675,7 @@ __global__ __launch_bounds__(kCfyBlock) __attribute__((amdgpu_waves_per_eu(MGPU_
       uint32_t cl[kPts];
       uint64_t ge[kPts];
       if constexpr (kStaged) {
-        raster_class_batch<kPts>(t, s_blk, s_band, ri, bi, sb, cl);
+        raster_class_batch<kPts, FINE>(t, s_blk, s_band, ri, bi, sb, cl);
 #pragma unroll
         for (int j = 0; j < kPts; j++) ge[j] = 0ull;
       } else {
@@ -1713,7 +1752,12 @@ __global__ __launch_bounds__(kCfyBlock) __attribute__((amdgpu_waves_per_eu(MGPU_
       }
     }
   };
-  cfy_dispatch<IS>(cfy_staged(t, nblk), a.valid != nullptr, run);
+  if constexpr (FINE) {
+    if (a.valid != nullptr) run(std::true_type{}, std::true_type{});
+    else run(std::true_type{}, std::false_type{});
+  } else {
+    cfy_dispatch<IS>(cfy_staged(t, nblk), a.valid != nullptr, run);
+  }
   count_wave(&a.counters[2], any_bad);
 }
 
@@ -3383,6 +3427,59 @@ static void launch_emit(const SplitArgs& a, int64_t nc, hipStream_t s) {
   hipLaunchKernelGGL(split_emit_kernel<IS>, dim3((unsigned)nc), dim3(kClsBlock), lds, s, a);
 }
 
+// One thread per block of the finer table (chip_table.h raster_fine): the block's pixels,
+// clipped at the raster's edges, share a class below kFineLookup -- that class -- or not.
+// (A refined pixel, >= 0x8000, and kPixMixed are above it.)
+__global__ __launch_bounds__(256) void fine_table_kernel(const uint16_t* raster, uint32_t nx, uint32_t ny, uint32_t sx,
+                                                         uint32_t sy, uint32_t bnx, uint32_t nfine, uint8_t* out) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= nfine) return;
+  const uint32_t x0 = (i % bnx) << sx, y0 = (i / bnx) << sy;
+  const uint32_t x1 = min(x0 + (1u << sx), nx), y1 = min(y0 + (1u << sy), ny);
+  const uint32_t c = raster[(size_t)y0 * nx + x0];
+  bool same = true;
+  for (uint32_t y = y0; y < y1; y++)
+    for (uint32_t x = x0; x < x1; x++) same = same && raster[(size_t)y * nx + x] == c;
+  out[i] = (uint8_t)(same && c < kFineLookup ? c : kFineLookup);
+}
+
+bool fine_table_shape(const ChipTableView& t, uint32_t* sx, uint32_t* sy, uint32_t* bnx, uint32_t* bny) {
+  if (t.raster_mode != kRasterLonLat || !cfy_staged(t, t.raster_bnx * t.raster_bny)) return false;
+  const uint32_t shapes[3][2] = {{2, 2}, {3, 2}, {2, 3}};  // finest first
+  for (const auto& sh : shapes) {
+    const uint64_t nx = ((uint64_t)t.raster_nx + (1u << sh[0]) - 1) >> sh[0], ny = ((uint64_t)t.raster_ny + (1u << sh[1]) - 1) >> sh[1];
+    if (nx * ny > kCfyFineLds || cfy_fine_lds((uint32_t)(nx * ny), t.raster_nband) > kCfyFineLds) continue;
+    *sx = sh[0], *sy = sh[1], *bnx = (uint32_t)nx, *bny = (uint32_t)ny;
+    return true;
+  }
+  return false;
+}
+
+hipError_t launch_fine_table(const ChipTableView& t, uint32_t sx, uint32_t sy, uint32_t bnx, uint32_t bny, uint8_t* out,
+                             hipStream_t s) {
+  const uint32_t nfine = bnx * bny;
+  if (hipError_t e = hipMemsetAsync(out, (int)kFineLookup, ((size_t)nfine + 3) & ~(size_t)3, s)) return e;  // (the padding too)
+  hipLaunchKernelGGL(fine_table_kernel, dim3((nfine + 255) / 256), dim3(256), 0, s, t.raster, t.raster_nx, t.raster_ny, sx,
+                     sy, bnx, nfine, out);
+  return hipGetLastError();
+}
+
+// The classify pass over a table with raster_fine: kCfyFineBlock threads per workgroup.
+static void launch_classify_fine(const SplitArgs& a, int64_t nc, hipStream_t s) {
+  const ChipTableView& ct = a.j.chips;
+  const size_t lds = cfy_fine_lds(ct.fine_bnx * ct.fine_bny, ct.raster_nband);
+  const int64_t wg = (nc + kCfyFineBlock / 64 - 1) / (kCfyFineBlock / 64);
+  auto go = [&](auto kernel) {
+    if (lds > 64 * 1024) hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const int64_t grid = std::min<int64_t>(wg, (int64_t)resident_blocks((const void*)kernel, kCfyFineBlock, lds));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kCfyFineBlock), lds, s, a, nc);
+  };
+  if (MGPU_CFY_PAIR && ((((uintptr_t)a.j.x) | ((uintptr_t)a.j.y)) & 15) == 0)
+    go(classify_pair_kernel<MGPU_H3, kCfyFineBlock, true>);
+  else
+    go(classify_wave_kernel<MGPU_H3, kCfyFineBlock, true>);
+}
+
 template <int IS>
 static void launch_split_t(const SplitArgs& a, hipStream_t s, hipEvent_t after_classify, hipEvent_t after_mixed, bool emit) {
   const int64_t nc = split_chunks(a.j.n);
@@ -3390,11 +3487,14 @@ static void launch_split_t(const SplitArgs& a, hipStream_t s, hipEvent_t after_c
   const size_t nblk = (IS == MGPU_H3 && ct.raster_blk) ? (size_t)ct.raster_bnx * ct.raster_bny : 0;
   const size_t lds = IS == MGPU_H3 ? ((nblk + 1) & ~(size_t)1) * 2 + (size_t)ct.raster_nband * 4 : 0;
   const int64_t wg = (nc + kCfyBlock / 64 - 1) / (kCfyBlock / 64);
-  if (lds > 64 * 1024) {  // (a block table beyond 64 KB: one workgroup per CU)
+  const bool fine = IS == MGPU_H3 && ct.raster_fine;
+  if (!fine && lds > 64 * 1024) {  // (a block table beyond 64 KB: one workgroup per CU)
     hipFuncSetAttribute((const void*)classify_pair_kernel<IS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipFuncSetAttribute((const void*)classify_wave_kernel<IS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   }
-  if (MGPU_CFY_PAIR && ((((uintptr_t)a.j.x) | ((uintptr_t)a.j.y)) & 15) == 0) {
+  if (fine) {
+    launch_classify_fine(a, nc, s);
+  } else if (MGPU_CFY_PAIR && ((((uintptr_t)a.j.x) | ((uintptr_t)a.j.y)) & 15) == 0) {
     const int64_t grid = std::min<int64_t>(wg, (int64_t)resident_blocks((const void*)classify_pair_kernel<IS>, kCfyBlock, lds));
     hipLaunchKernelGGL(classify_pair_kernel<IS>, dim3((unsigned)grid), dim3(kCfyBlock), lds, s, a, nc);
   } else {

@@ -30,7 +30,8 @@ MGPU_HDI uint32_t div_fix(uint32_t v, uint32_t d, double inv) {
   const uint32_t q = (uint32_t)((double)v * inv);
   return q * d > v ? q - 1 : ((q + 1) * d <= v ? q + 1 : q);
 }
-template <int IS>
+// FINE (lonlat with raster_fine): *blk = the pixel's block of the finer table instead.
+template <int IS, bool FINE = false>
 MGPU_HDI uint32_t raster_index(const ChipTableView& t, double px, double py, bool* ok, uint32_t* gi, uint32_t* sub,
                                uint32_t* blk = nullptr) {
   if (blk) *blk = kNoPixel;
@@ -60,7 +61,11 @@ MGPU_HDI uint32_t raster_index(const ChipTableView& t, double px, double py, boo
   uint32_t ix = (uint32_t)tx, iy = (uint32_t)ty;
   ix = ix < t.raster_nx ? ix : t.raster_nx - 1;
   iy = iy < t.raster_ny ? iy : t.raster_ny - 1;
-  if (blk && t.raster_bshift) *blk = (iy >> t.raster_bshift) * t.raster_bnx + (ix >> t.raster_bshift);
+  if (FINE) {
+    if (blk) *blk = (iy >> t.fine_sy) * t.fine_bnx + (ix >> t.fine_sx);
+  } else if (blk && t.raster_bshift) {
+    *blk = (iy >> t.raster_bshift) * t.raster_bnx + (ix >> t.raster_bshift);
+  }
   if (t.raster_sub_n) {
     const double S = (double)t.raster_sub_n;
     uint32_t u = (uint32_t)((tx - (double)ix) * S), v = (uint32_t)((ty - (double)iy) * S);
